@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — video-tokens/sec through ViT + Q-Former + projector + Vicuna-7B prefill (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dtype bf16|fp16|fp32|bf16x3] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dtype bf16|fp16|fp32|bf16x3] [--full] [--no-cpu-baseline]
+                    [--dump-outputs DIR]
+
+A plain run (no --full) sets up, warms up, times the K steps and prints the headline line: `metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` (+ the workload's description and the timed bracket's per-block times).  Everything else the benchmark measures or
+checks is behind `--full`: the parity against the reference fixture, the roofline of the dominant GEMM symbol, the device telemetry, the
+single-stream bracket, the fp16 / fp32 / split-verify legs, the frame_parallel_projection block (N = 1), the frame_parallel block (N > 1)
+and the CPU baseline (the `--no-*` switches below each turn one of them off again inside a `--full` run).
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy (float32; see dump_outputs).
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: bench.py starts the N ranks itself (one process per GPU,
 rendezvous on 127.0.0.1); under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` it uses the
@@ -25,11 +33,11 @@ point-to-point exchange of the team's token sub-blocks] -> pooling -> token-bloc
   --config c5 (BASELINE.json configs[4]; reference config/minigpt4base_stllm_qa.yaml:3,7,11,13-14): BT-Adapter backbone (temporal + spatial
       side branch on the last 3 ViT blocks), T=16, 'all' pooling, mask + MVM.  One clip per GPU (the backbone shards by clip only).
       c3 / c4 / c5 each have a full-size reference fixture (tests/golden/c{3,4,5}_full.npz): their lines carry `parity` like c2's.
-  At N > 1 the default (c2) run ALSO carries the north star's frame-parallel experiment in the same invocation (no extra flag):
+  At N > 1 the c2 run with --full ALSO carries the north star's frame-parallel experiment in the same invocation:
       after the c2 timing the ranks build config c3, rank 0 times it ALONE (1-GPU reference, the other ranks wait at a barrier),
       then all N ranks time it as clip teams -> "frame_parallel": {ms_per_step_1gpu, ms_per_step + speedup (steps back to back),
       latency_ms + latency_speedup (one batch between barriers), plan, token_exchange_us, frames_per_rank, received_blocks_bit_identical}.
-  At N = 1 (c2) the line also carries an fp16 leg, the fp32 "verify" leg and the SPLIT verify leg (bf16x3: three bf16 matrix-core products
+  At N = 1 (c2) the --full line also carries an fp16 leg, the fp32 "verify" leg and the SPLIT verify leg (bf16x3: three bf16 matrix-core products
       per Linear, fp32 everything else) — ms_per_step + parity each — next to the timed bf16, a `frame_parallel_projection` block (config c3
       timed on this one GPU, then every kind of rank at N = 2 / 4 / 8 played alone on it: throughput_ms and latency_ms from the measured shares + a MODELLED wire),
       the device's clock / power over the timed region (`telemetry`) and the timed region's per-block times (`ms_per_step_blocks`).
@@ -224,6 +232,33 @@ def parity_vs_fixture(logits, loss, name="c2_full", mask=None):
     if mask is not None and "mask" in g.files:   # the mask bench.py drew with the package's generator == the one the reference drew
         res["mask_equals_reference"] = bool(np.array_equal(np.asarray(mask).astype(bool), g["mask"].astype(bool)))
     return res
+
+
+DUMP_LOGITS_BYTES = 48 << 20   # c2's logits are 576 x 32000 fp32 = 70 MiB: more than the 64 MB a dump may hold
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: what the timed step returned to its caller, as float32 .npy files under `path` — `loss`, `loss_mvm` (MVM configs) and
+    `logits`, flattened to [rows, vocab].  Logits above DUMP_LOGITS_BYTES are a fixed sample of their rows (numpy seed 0, ascending; the same
+    rows for the same shape): `logits_rows` holds the row numbers.  Two builds run with the same arguments are compared file for file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name in ("loss", "loss_mvm"):
+        v = getattr(out, name, None)
+        if v is not None:
+            arrays[name] = v.detach().float().cpu().numpy().reshape(-1)
+    if out.logits is not None:
+        lg = out.logits.detach().float().cpu().numpy()
+        lg = lg.reshape(-1, lg.shape[-1])
+        if lg.nbytes > DUMP_LOGITS_BYTES:
+            rows = np.sort(np.random.default_rng(0).choice(lg.shape[0], DUMP_LOGITS_BYTES // lg[0].nbytes, replace=False))
+            arrays["logits_rows"] = rows.astype(np.float32)
+            lg = lg[rows]
+        arrays["logits"] = np.ascontiguousarray(lg, dtype=np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def load_traffic(kernel):
@@ -771,7 +806,7 @@ def _run(args, world, rank, device, dry):
     S_local = (out.sp_rows[1] if getattr(out, "sp_rows", None) else out.logits.shape[1]) if out.logits is not None else 0   # (sequence-parallel: the clip's length = the last member's end)
     S_un = (S_local - sm.mask_img_len + sm.img_len) if (mask is not None and out.logits is not None) else 0   # the MVM branch's second prefill
     parity = None
-    if rank == 0 and out.logits is not None and world == 1 and not dry and B == (conf["clips"] or 1):
+    if args.full and rank == 0 and out.logits is not None and world == 1 and not dry and B == (conf["clips"] or 1):
         parity = parity_vs_fixture(out.logits, float(out.loss.item()), name=f"{args.config}_full", mask=mask)
     prof = None
     cal = {}
@@ -792,7 +827,7 @@ def _run(args, world, rank, device, dry):
     # inside the run (clock ramps, a throttling box); ms_per_step is still the whole bracket, block boundaries included.
     nb = 3 if args.steps >= 6 else 1
     bsz = [args.steps // nb + (1 if i < args.steps % nb else 0) for i in range(nb)]
-    tele = Telemetry(device.index or 0).start() if (rank == 0 and not dry) else None
+    tele = Telemetry(device.index or 0).start() if (args.full and rank == 0 and not dry) else None
     block_ms = []
     sync()
     t0 = time.perf_counter()
@@ -811,13 +846,15 @@ def _run(args, world, rank, device, dry):
     if prof is not None:
         target_summary = prof.summary().get(prof.target)
         prof.stop()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
     # ---- clips in flight (round 6): with streams > 1 the bracket above ran step k on HIP stream k % streams — every step is still one whole B = 1 pass
     # (encode + prefill + lm_head + loss), two of them share the chip: the small kernels' idle CUs, every launch's cold start and tail are covered by the
-    # other clip's kernels.  The SAME K-step loop on ONE stream follows (its own bracket, after the headline): the one-clip-at-a-time rate, and the bracket
+    # other clip's kernels.  With --full the SAME K-step loop on ONE stream follows (its own bracket, after the headline): the one-clip-at-a-time rate, and the bracket
     # in which the dominant kernel's own duration is sampled (an event pair around a launch that shares the chip with another stream's kernel times both).
     single_stream = None
     inflight_summary = None
-    if streams:
+    if streams and args.full:
         n1 = max(10, args.steps // 2)
         inflight_summary = target_summary
         saved, streams[:] = list(streams), []
@@ -888,6 +925,7 @@ def _run(args, world, rank, device, dry):
                "end_to_end_tflops_per_gpu": round(B * flop_clip / step_s / 1e12 / world, 1)}
         if streams:
             res["clips_in_flight"] = n_streams
+        if single_stream is not None:
             res["single_stream"] = dict(single_stream, value=round(B * Lvis / (single_stream["ms_per_step"] * 1e-3), 2), unit="video-tokens/s",
                                         note="the same step loop on ONE stream (one clip at a time: the latency of a clip), its own bracket right after the headline's")
         if world > 1:
@@ -899,7 +937,7 @@ def _run(args, world, rank, device, dry):
             if conf["scaling"] == "weak":
                 res["scaling_note"] = ("weak scaling: one clip per GPU — every rank is a clip team of one, nothing is exchanged inside the step "
                                        "(token_exchange_in_step false); the frame-parallel strong-scaling experiment (config c3: clip teams, point-to-point "
-                                       "exchange, sequence-parallel prefill) is the frame_parallel block of this line")
+                                       "exchange, sequence-parallel prefill) is the frame_parallel block of the --full line")
             if fp_leg is not None:
                 res["frame_parallel"] = fp_leg
         if dry:
@@ -1019,7 +1057,14 @@ def main():
     ap.add_argument("--fp-clips", type=int, default=0, help="override the c3 block's clips per batch (debugging / dry runs: 1 clip on 2 ranks = one team of two)")
     ap.add_argument("--fp-steps-1gpu", type=int, default=3, help="timed steps of the c3 block's 1-GPU reference (rank 0 alone)")
     ap.add_argument("--dry-cpu", action="store_true", help="run the rank logic on CPU (gloo, contract backend): plumbing check only")
+    ap.add_argument("--full", action="store_true", help="also run every other measurement and check (parity, roofline, telemetry, single-stream bracket, "
+                                                        "numerics legs, frame-parallel blocks, CPU baseline); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run times the headline and nothing else
+        args.no_roofline = args.no_cpu_baseline = args.no_extra_legs = args.no_projection = args.no_frame_parallel = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
     run_rank(args)

@@ -25,7 +25,7 @@ def _run(extra, timeout=900, threads=None):
 
 @pytest.mark.parametrize("config,scaling,batch", [("c3", "strong", 4), ("c2", "weak", 2)])
 def test_bench_self_spawns_two_ranks(config, scaling, batch):
-    res = _run(["--gpus", "2", "--config", config, "--fp-clips", "1"])
+    res = _run(["--gpus", "2", "--config", config, "--fp-clips", "1", "--full"])
     assert res["n_gpus"] == 2 and res["scaling"] == scaling and res["config"]["name"] == config
     assert res["config"]["global_batch"] == batch and res["steps"] == 1 and res["higher_is_better"] is True
     assert res["value"] > 0 and res["ms_per_step"] > 0
@@ -38,7 +38,7 @@ def test_bench_self_spawns_two_ranks(config, scaling, batch):
         assert res["plan"]["teams"] == [[0], [1], [0], [1]]
         assert "frame_parallel" not in res            # the c3 line IS the frame-parallel experiment
     else:
-        # the driver's `bench.py --gpus N` (no --config) must carry the north star's experiment: c3 strong scaling, rank 0 alone first, then all
+        # `bench.py --gpus N --full` (no --config) must carry the north star's experiment: c3 strong scaling, rank 0 alone first, then all
         # ranks as clip teams (here --fp-clips 1: ONE clip on 2 ranks = a team of two, 1 frame each, point-to-point exchange, sequence-parallel
         # prefill), the received blocks checked against the single-GPU encode, throughput AND one-batch latency timed
         fp = res["frame_parallel"]
@@ -54,10 +54,10 @@ def test_bench_self_spawns_two_ranks(config, scaling, batch):
 
 
 def test_bench_self_spawns_eight_ranks_clip_teams_of_two():
-    """VERDICT r05 #8c: the N = 8 plan of the driver's `bench.py --gpus 8` — c3's 4 clips as 4 teams of 2 ranks, point-to-point token exchange,
+    """VERDICT r05 #8c: the N = 8 plan of `bench.py --gpus 8 --full` — c3's 4 clips as 4 teams of 2 ranks, point-to-point token exchange,
     sequence-parallel prefill inside every team, the loss run along the team — executed end to end by 8 gloo processes (contract backend, reduced depth:
     plumbing, not a measurement; no byte has crossed RCCL for this repository yet)."""
-    res = _run(["--gpus", "8", "--config", "c2"], timeout=1500, threads=1)
+    res = _run(["--gpus", "8", "--config", "c2", "--full"], timeout=1500, threads=1)
     assert res["n_gpus"] == 8 and res["rccl_ranks"] == 8 and res["config"]["global_batch"] == 8 and res["value"] > 0
     assert res["plan"]["teams"] == [[r] for r in range(8)] and res["token_exchange_in_step"] is False     # c2 weak scaling: one clip per rank, nothing on the wire
     fp = res["frame_parallel"]
@@ -71,10 +71,10 @@ def test_bench_self_spawns_eight_ranks_clip_teams_of_two():
 
 
 def test_bench_single_rank_line_carries_projection_blocks_and_telemetry_keys():
-    """N = 1 (the driver's BENCH run): the c2 line must carry the frame_parallel_projection block (c3 on one GPU, every kind of rank of the
+    """N = 1, --full: the c2 line must carry the frame_parallel_projection block (c3 on one GPU, every kind of rank of the
     TeamPlan at N = 2 / 4 / 8 played alone: throughput_ms AND latency_ms from the measured shares + a modelled wire, labelled unmeasured),
     ms_per_step_blocks and the telemetry key (null without a GPU)."""
-    res = _run(["--gpus", "1"])
+    res = _run(["--gpus", "1", "--full"])
     assert res["n_gpus"] == 1 and res["config"]["name"] == "c2" and res["steps"] == 1
     assert res["ms_per_step_blocks"]["steps"] == [1] and len(res["ms_per_step_blocks"]["ms"]) == 1 and "telemetry" in res
     pj = res["frame_parallel_projection"]
@@ -101,9 +101,9 @@ def test_bench_single_rank_line_carries_projection_blocks_and_telemetry_keys():
 
 
 def test_bench_watchdog_keeps_the_headline_when_the_frame_parallel_block_stalls():
-    """the c3 block has never run on a multi-GPU node: if it does not finish in --fp-timeout seconds, rank 0 still prints the (complete) headline line,
+    """the c3 block (--full) has never run on a multi-GPU node: if it does not finish in --fp-timeout seconds, rank 0 still prints the (complete) headline line,
     with the reason in place of the block, and every rank exits 0"""
-    res = _run(["--gpus", "2", "--fp-clips", "1", "--fp-timeout", "0.5"])
+    res = _run(["--gpus", "2", "--fp-clips", "1", "--fp-timeout", "0.5", "--full"])
     assert res["n_gpus"] == 2 and res["value"] > 0 and res["ms_per_step"] > 0
     assert "watchdog" in res["frame_parallel"]["error"]
 
@@ -116,6 +116,43 @@ def test_bench_mvm_configs_dry(config):
     assert res["config"]["name"] == config and "MVM branch" in res["config"]["workload"] and res["loss"] == res["loss"]
     assert ("BT-Adapter" in res["config"]["workload"]) == (config == "c5")
     assert res["config"]["video_tokens_per_clip"] == 2 * 32
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """without --full the line is the headline of exactly --steps timed steps: no parity, roofline, telemetry, single-stream bracket, numerics legs,
+    projection or CPU baseline; --dump-outputs writes what the last timed step returned (float32 .npy)"""
+    import numpy as np
+    res = _run(["--gpus", "1", "--steps", "2", "--dump-outputs", str(tmp_path / "out")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in res, k
+    assert res["steps"] == 2 and res["ms_per_step_blocks"]["steps"] == [2] and res["value"] > 0 and res["ms_per_step"] > 0
+    for k in ("parity", "roofline", "single_stream", "fp16", "frame_parallel_projection", "frame_parallel", "cpu_baseline"):
+        assert k not in res, k
+    assert res["telemetry"] is None
+    loss, logits = np.load(tmp_path / "out" / "loss.npy"), np.load(tmp_path / "out" / "logits.npy")
+    assert loss.dtype == np.float32 and logits.dtype == np.float32
+    assert loss.shape == (1,) and abs(float(loss[0]) - res["loss"]) < 1e-4
+    assert logits.shape == (res["config"]["seq_len"], 32000) and np.isfinite(logits).all()
+    assert not (tmp_path / "out" / "logits_rows.npy").exists()      # small enough to be written whole
+
+
+def test_dump_outputs_samples_large_logits_with_a_fixed_seed(tmp_path):
+    """logits above the dump's budget: a fixed sample of their rows (the same rows every run), stored with the row numbers; the whole dump stays under 64 MB"""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    lg = torch.randn(1, 576, 32000)
+    out = types.SimpleNamespace(loss=torch.tensor(2.5), loss_mvm=None, logits=lg)
+    assert bench.dump_outputs(out, str(tmp_path / "a")) == ["logits", "logits_rows", "loss"]
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    rows = np.load(tmp_path / "a" / "logits_rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "logits_rows.npy"))
+    r = rows.astype(np.int64)
+    assert (np.diff(r) > 0).all() and r[0] >= 0 and r[-1] < 576 and len(r) == bench.DUMP_LOGITS_BYTES // (32000 * 4)
+    assert np.array_equal(np.load(tmp_path / "a" / "logits.npy"), lg[0, r].numpy())
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64e6
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == 2.5
 
 
 def test_bench_launcher_environment_is_honoured(monkeypatch):

@@ -6,7 +6,7 @@ out=$1; reps=$2; shift 2
 for r in $(seq 1 $reps); do
   for arm in "$@"; do
     echo "== $arm" >> $out
-    env $arm python bench.py --steps 50 --warmup 5 --no-extra-legs --no-cpu-baseline --no-projection 2>/dev/null | python -c '
+    env $arm python bench.py --full --steps 50 --warmup 5 --no-extra-legs --no-cpu-baseline --no-projection 2>/dev/null | python -c '
 import json, sys
 d = json.loads(sys.stdin.readlines()[-1])
 print("ms_per_step", d["ms_per_step"], "blocks", d.get("ms_per_step_blocks", {}).get("ms"), "sclk", d.get("telemetry", {}).get("sclk_mhz", {}).get("mean"))
