@@ -239,6 +239,28 @@ typedef struct {
 int64_t stllm_llama_layers_scratch_bytes(int dtype, int B, int S, int hidden, int inter);
 /* the decoder-layer loop of the PREFILL (st_llm.py:56-92 -> HF LlamaModel.forward, use_cache False or filling a fresh cache) */
 int stllm_llama_layers(const stllm_llama_layers_args* args, const stllm_llama_layer_weights* layers, int n_layers, void* stream);
+/* ---- LoRA adapters on q_proj / v_proj (peft 0.8.1 Linear, eval: y = W x + (lora_alpha / r) B (A x); the reference builds them at st_llm.py:165-177).  Additive to
+ * ABI 7: new symbols only, no existing struct changes.
+ *
+ * stllm_lora_down: out[M, n_pad] = x[M, K] · A[n, K]^T in T (fp32 accumulation), columns [n, n_pad) written as zeros.  A = [lora_A(q_proj) ; lora_A(v_proj)]
+ * (n = 2 r).  K is split over workgroups and reduced in a fixed order (no atomics): two calls on the same input give the same bits.  1 <= M, n <= n_pad <= 128,
+ * n_pad % 32 == 0, K a whole number of 128-byte panels, rows 16-byte aligned; x and out may be column ranges of ONE row buffer (ldx == ldo).
+ * workspace: >= stllm_lora_down_workspace_bytes(dtype, M, K, n_pad) bytes (0 for tall problems). */
+int64_t stllm_lora_down_workspace_bytes(int dtype, int M, int K, int n_pad);
+int stllm_lora_down(int dtype, const void* x, int64_t ldx, const void* A, int64_t lda, void* out, int64_t ldo, int M, int K, int n, int n_pad,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+/* adapter of one decoder layer: A [2 r, hidden] in T (q rows, then v rows); wqkv_ext [3 hidden, hidden + P] in T = the layer's packed wqkv with P extra columns:
+ * q rows (in the packed RoPE head order) [s B_q | 0], k rows 0, v rows [0 (r columns) | s B_v | 0], s = lora_alpha / r; P = 2 r rounded up to the GEMMs' K
+ * granularity (64 columns in 16 bits, 32 in fp32), the same for every layer of a call. */
+typedef struct {
+  const void* A; int64_t ld_a;
+  const void* wqkv_ext; int64_t ld_ext;
+  int r; int P;
+} stllm_llama_lora_layer;
+int64_t stllm_llama_layers_lora_scratch_bytes(int dtype, int B, int S, int hidden, int inter, int P);
+/* stllm_llama_layers with active adapters — still ONE call per prefill: per layer RMSNorm -> stllm_lora_down -> ONE QKV GEMM over K = hidden + P (the low-rank
+ * term joins the fp32 accumulator BEFORE the RoPE epilogue; layers[l].wqkv / wqkv_frag are not read) -> the rest of the base layer.  bf16 / fp16 / fp32. */
+int stllm_llama_layers_lora(const stllm_llama_layers_args* args, const stllm_llama_layer_weights* layers, const stllm_llama_lora_layer* lora_layers, int n_layers, void* stream);
 /* ONE decoder layer of a SEQUENCE-PARALLEL prefill in two parts (ABI >= 7, round 6; st-llm_amd/models/llama.py: LlamaModel.prefill_sp — no reference counterpart, the
  * reference has no sequence parallelism: SURVEY.md 2b): this rank owns the positions [s0, s1) of one sequence (args->B == 1, args->S == s1 - s0 rows in x,
  * args->rope_cos / rope_sin pointing at position s0's table row), `qkv` is the fused buffer [s1, 3 * hidden] (compute dtype) whose rows [0, s0) hold the earlier

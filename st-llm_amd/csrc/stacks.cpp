@@ -10,6 +10,11 @@
 
 void stllm_set_error(const char* fmt, ...);
 
+// csrc/lora.hip is not in every library this file is linked into (the host-emulated test build takes stacks.cpp with a subset of the kernels):
+// weak references, checked by the one entry point that needs them
+#pragma weak stllm_lora_down
+#pragma weak stllm_lora_down_workspace_bytes
+
 namespace {
 
 inline int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
@@ -147,7 +152,10 @@ extern "C" int64_t stllm_llama_layers_scratch_bytes(int dtype, int B, int S, int
 //   RMSNorm -> [fused QKV GEMM + rotate-half RoPE] -> causal attention (+ right-padding kv_len) -> [o_proj + residual] -> RMSNorm ->
 //   [gate/up GEMM + SiLU(gate) * up] -> [down_proj + residual].   With kv_cache pointers the fused QKV rows of layer l are written
 //   into its cache buffer [B, cache_max_len, 3 * hidden] (rows (b, s) at b * cache_max_len + s) and attended in place.
-extern "C" int stllm_llama_layers(const stllm_llama_layers_args* a, const stllm_llama_layer_weights* layers, int n_layers, void* stream) {
+// lora == nullptr: the base stack.  Otherwise (stllm_llama_layers_lora) layer l's QKV GEMM runs on the K-extended operands: the RMSNorm writes h into rows
+// of D + P columns, stllm_lora_down puts t = h [A_q ; A_v]^T (+ zero pad) behind it, and ONE GEMM of K = D + P over lora[l].wqkv_ext adds s B t in the
+// fp32 accumulator before the RoPE epilogue.  Everything after the QKV rows is the base stack's.
+static int llama_layers_impl(const stllm_llama_layers_args* a, const stllm_llama_layer_weights* layers, const stllm_llama_lora_layer* lora, int n_layers, void* stream) {
   if (!a || (!layers && n_layers > 0) || n_layers < 0) { stllm_set_error("stllm_llama_layers: null arguments"); return STLLM_ERR_BAD_SHAPE; }
   if (!dtype_ok(a->dtype)) { stllm_set_error("stllm_llama_layers: bad dtype %d", a->dtype); return STLLM_ERR_BAD_DTYPE; }
   if (a->n_heads <= 0 || a->hidden <= 0 || a->inter <= 0 || a->B <= 0 || a->S <= 0 || a->hidden % a->n_heads != 0 || a->ldx < a->hidden ||
@@ -155,20 +163,31 @@ extern "C" int stllm_llama_layers(const stllm_llama_layers_args* a, const stllm_
     stllm_set_error("stllm_llama_layers: bad dims (heads %d, hidden %d, inter %d, ldx %lld) / null buffers", a->n_heads, a->hidden, a->inter, (long long)a->ldx);
     return STLLM_ERR_BAD_SHAPE;
   }
-  const int64_t need = stllm_llama_layers_scratch_bytes(a->dtype, a->B, a->S, a->hidden, a->inter);
+  const int P = lora && n_layers > 0 ? lora[0].P : 0;
+  if (lora) {
+    if (a->dtype == STLLM_BF16X3) { stllm_set_error("stllm_llama_layers_lora: the split mode runs merged adapters only"); return STLLM_ERR_BAD_DTYPE; }
+    for (int l = 0; l < n_layers; ++l)
+      if (!lora[l].A || !lora[l].wqkv_ext || lora[l].P != P || lora[l].r < 8 || lora[l].r > 64 || lora[l].r % 8 != 0 || 2 * lora[l].r > P || P > 128 || P % 32 != 0 ||
+          lora[l].ld_a < a->hidden || lora[l].ld_ext < a->hidden + P) {
+        stllm_set_error("stllm_llama_layers_lora: layer %d: bad adapter descriptor (r %d, P %d; r a multiple of 8 in [8, 64], one P for all layers)", l, lora[l].r, lora[l].P);
+        return STLLM_ERR_BAD_SHAPE;
+      }
+  }
+  const int64_t need = lora ? stllm_llama_layers_lora_scratch_bytes(a->dtype, a->B, a->S, a->hidden, a->inter, P)
+                            : stllm_llama_layers_scratch_bytes(a->dtype, a->B, a->S, a->hidden, a->inter);
   if (need < 0 || a->scratch_bytes < need) {
     stllm_set_error("stllm_llama_layers: scratch of %lld bytes needed, %lld given", (long long)need, (long long)a->scratch_bytes);
     return STLLM_ERR_BAD_SHAPE;
   }
   const int M = a->B * a->S, D = a->hidden, hd = D / a->n_heads, e = esize(a->dtype), eh = (int)hsize(a->dtype);
   const bool x3 = a->dtype == STLLM_BF16X3;
-  const int64_t ldh = x3 ? 3 * (int64_t)D : D, ldg = x3 ? 3 * (int64_t)a->inter : a->inter;
+  const int64_t ldh = x3 ? 3 * (int64_t)D : D + P, ldg = x3 ? 3 * (int64_t)a->inter : a->inter;
   if (a->cache_max_len != 0 && (a->cache_max_len < a->S || a->kv_len != nullptr)) {
     stllm_set_error("stllm_llama_layers: the KV cache needs max_len >= S and equal-length sequences");
     return STLLM_ERR_BAD_SHAPE;
   }
   Carver c(a->scratch, a->scratch_bytes);
-  char* h = reinterpret_cast<char*>(c.take((int64_t)M * D * eh));
+  char* h = reinterpret_cast<char*>(c.take((int64_t)M * (D + P) * eh));
   char* att = reinterpret_cast<char*>(c.take((int64_t)M * D * e));
   char* qkv_s = reinterpret_cast<char*>(c.take((int64_t)M * 3 * D * e));
   char* gu = reinterpret_cast<char*>(c.take((int64_t)M * a->inter * eh));
@@ -177,6 +196,13 @@ extern "C" int stllm_llama_layers(const stllm_llama_layers_args* a, const stllm_
   if (a->dtype == STLLM_BF16X3) {
     sws_bytes = llama_split_ws(M, D, a->inter);
     sws = c.take(sws_bytes);
+  }
+  void* dws = nullptr;
+  int64_t dws_bytes = 0;
+  if (lora) {
+    dws_bytes = stllm_lora_down_workspace_bytes(a->dtype, M, D, P);
+    if (dws_bytes < 0) { stllm_set_error("stllm_llama_layers_lora: hidden %d / P %d outside the down projection's shapes", D, P); return STLLM_ERR_BAD_SHAPE; }
+    dws = c.take(dws_bytes);
   }
   const int adt = act_dtype(a->dtype);
   const float scale = (float)(1.0 / __builtin_sqrt((double)hd));
@@ -188,6 +214,10 @@ extern "C" int stllm_llama_layers(const stllm_llama_layers_args* a, const stllm_
     if (x3) g.split_flags = STLLM_SPLIT_A_PRESPLIT;
     else g.w_frag = w.wqkv_frag;
     g.aux0 = a->rope_cos; g.aux1 = a->rope_sin; g.rope_seq = a->S; g.rope_cols = 2 * D; g.M = M; g.N = 3 * D; g.K = D; g.ldo = 3 * D;
+    if (lora) {
+      STACK_TRY(stllm_lora_down(a->dtype, h, ldh, lora[l].A, lora[l].ld_a, h + (int64_t)D * e, ldh, M, D, 2 * lora[l].r, P, dws, dws_bytes, stream));
+      g.W = lora[l].wqkv_ext; g.ldw = lora[l].ld_ext; g.w_frag = nullptr; g.K = D + P;
+    }
     char* qkv = qkv_s;
     int64_t bs = (int64_t)a->S * 3 * D;
     if (a->cache_max_len != 0) {
@@ -219,6 +249,25 @@ extern "C" int stllm_llama_layers(const stllm_llama_layers_args* a, const stllm_
     STACK_TRY(stllm_gemm(&g, stream));
   }
   return STLLM_OK;
+}
+
+extern "C" int stllm_llama_layers(const stllm_llama_layers_args* a, const stllm_llama_layer_weights* layers, int n_layers, void* stream) {
+  return llama_layers_impl(a, layers, nullptr, n_layers, stream);
+}
+
+extern "C" int64_t stllm_llama_layers_lora_scratch_bytes(int dtype, int B, int S, int hidden, int inter, int P) {
+  if (!&stllm_lora_down_workspace_bytes || dtype == STLLM_BF16X3 || P <= 0 || P > 128 || P % 32 != 0) return -1;
+  const int64_t base = stllm_llama_layers_scratch_bytes(dtype, B, S, hidden, inter);
+  if (base < 0) return -1;
+  const int64_t M = (int64_t)B * S, dws = stllm_lora_down_workspace_bytes(dtype, (int)M, hidden, P);
+  if (dws < 0) return -1;
+  return base - up256(M * hidden * esize(dtype)) + up256(M * (hidden + P) * esize(dtype)) + up256(dws);
+}
+
+extern "C" int stllm_llama_layers_lora(const stllm_llama_layers_args* a, const stllm_llama_layer_weights* layers, const stllm_llama_lora_layer* lora, int n_layers, void* stream) {
+  if (!&stllm_lora_down || !&stllm_lora_down_workspace_bytes) { stllm_set_error("stllm_llama_layers_lora: this library was built without csrc/lora.hip"); return STLLM_ERR_UNSUPPORTED; }
+  if (!lora && n_layers > 0) { stllm_set_error("stllm_llama_layers_lora: null adapter table (the base stack is stllm_llama_layers)"); return STLLM_ERR_BAD_SHAPE; }
+  return llama_layers_impl(a, layers, lora, n_layers, stream);
 }
 
 extern "C" int64_t stllm_llama_layer_sp_scratch_bytes(int dtype, int s0, int s1, int hidden, int inter) {

@@ -25,7 +25,8 @@ EXPORTS = ["stllm_last_error", "stllm_abi_version", "stllm_last_kernel", "stllm_
            "stllm_preprocess_workspace_bytes", "stllm_preprocess_frames", "stllm_attention_decode_workspace_bytes",
            "stllm_attention_decode", "stllm_gemm_profile", "stllm_gemm_profile_count", "stllm_gemm_profile_read",
            "stllm_vit_blocks_scratch_bytes", "stllm_vit_blocks", "stllm_llama_layers_scratch_bytes", "stllm_llama_layers", "stllm_llama_layer_sp_scratch_bytes", "stllm_llama_layer_sp",
-           "stllm_qformer_layers_scratch_bytes", "stllm_qformer_layers", "stllm_split3_rows", "stllm_gemm_split_ws_bytes"]
+           "stllm_qformer_layers_scratch_bytes", "stllm_qformer_layers", "stllm_split3_rows", "stllm_gemm_split_ws_bytes",
+           "stllm_lora_down_workspace_bytes", "stllm_lora_down", "stllm_llama_layers_lora_scratch_bytes", "stllm_llama_layers_lora"]
 
 
 def torch_dtype(d):
@@ -76,6 +77,10 @@ class LlamaLayersArgs(ctypes.Structure):
                 ("x", c_void_p), ("ldx", c_int64), ("rope_cos", c_void_p), ("rope_sin", c_void_p), ("kv_len", c_void_p),
                 ("cache_max_len", c_int64), ("scratch", c_void_p), ("scratch_bytes", c_int64),
                 ("workspace", c_void_p), ("workspace_bytes", c_int64)]
+
+
+class LlamaLoraLayer(ctypes.Structure):
+    _fields_ = [("A", c_void_p), ("ld_a", c_int64), ("wqkv_ext", c_void_p), ("ld_ext", c_int64), ("r", c_int), ("P", c_int)]
 
 
 class BertOutputWeights(ctypes.Structure):
@@ -151,6 +156,10 @@ def _bind(L, strict=True):
     B("stllm_llama_layer_sp", [ctypes.POINTER(LlamaLayersArgs), ctypes.POINTER(LlamaLayerWeights), c_void_p, c_int, c_int, c_int, c_void_p])
     B("stllm_qformer_layers_scratch_bytes", [c_int] * 9, c_int64)
     B("stllm_qformer_layers", [ctypes.POINTER(QformerLayersArgs), ctypes.POINTER(QformerLayerWeights), c_int, c_void_p])
+    B("stllm_lora_down_workspace_bytes", [c_int] * 4, c_int64)
+    B("stllm_lora_down", [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p])
+    B("stllm_llama_layers_lora_scratch_bytes", [c_int] * 6, c_int64)
+    B("stllm_llama_layers_lora", [ctypes.POINTER(LlamaLayersArgs), ctypes.POINTER(LlamaLayerWeights), ctypes.POINTER(LlamaLoraLayer), c_int, c_void_p])
     B("stllm_gemm_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     B("stllm_gemm_w4_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     return L
@@ -613,15 +622,56 @@ def llama_layer_array(layers, cache=None):
     return arr
 
 
-def llama_layers(x, layers, carr, *, B, S, n_heads, eps, rope, dtype, kv_len=None, cache=None):
+def lora_pad(r, dtype):
+    """P: the 2 r adapter columns rounded up to the K granularity of the GEMMs (one 128-byte panel: 64 columns in 16 bits, 32 in fp32)"""
+    panel = 32 if torch_dtype(dtype) == torch.float32 else 64
+    return (2 * r + panel - 1) // panel * panel
+
+
+def lora_down(x, A, *, dtype, out, M=None):
+    """out[M, n_pad] = x[M, K] @ A[n, K].T in the compute dtype, columns [n, n_pad) zeroed (stllm_lora_down; deterministic split-K).  x and out are
+    2-D views with unit column stride — in the model both are column ranges of one [M, K + n_pad] row buffer."""
+    td = torch_dtype(dtype)
+    _req(x, td, "x"); _req(A, td, "A"); _req(out, td, "out")
+    M = x.shape[0] if M is None else M
+    K, n, n_pad = x.shape[1], A.shape[0], out.shape[1]
+    if A.shape[1] != K or x.stride(1) != 1 or out.stride(1) != 1 or A.stride(1) != 1 or out.shape[0] < M:
+        raise RuntimeError(f"lora_down: x {tuple(x.shape)}, A {tuple(A.shape)}, out {tuple(out.shape)}")
+    L = lib()
+    code = dtype_code(td)
+    need = int(L.stllm_lora_down_workspace_bytes(code, M, K, n_pad))
+    if need < 0:
+        raise RuntimeError(f"lora_down: unsupported shape (M={M}, K={K}, n_pad={n_pad})")
+    ws = split_workspace(x.device, need) if need else None
+    _check(L.stllm_lora_down(code, _p(x), x.stride(0), _p(A), A.stride(0), _p(out), out.stride(0), M, K, n, n_pad, _p(ws), need, _stream()), "stllm_lora_down")
+    return out
+
+
+def llama_lora_array(layers):
+    """list of LlamaDecoderLayer.pack() dicts with active adapters -> ctypes array of stllm_llama_lora_layer (pk["wqkv"] IS the extended weight)"""
+    arr = (LlamaLoraLayer * len(layers))()
+    for i, pk in enumerate(layers):
+        w = arr[i]
+        w.A, w.ld_a = pk["lora_A"].data_ptr(), pk["lora_A"].stride(0)
+        w.wqkv_ext, w.ld_ext = pk["wqkv"].data_ptr(), pk["wqkv"].stride(0)
+        w.r, w.P = pk["lora_r"], pk["lora_P"]
+    return arr
+
+
+def llama_layers(x, layers, carr, *, B, S, n_heads, eps, rope, dtype, kv_len=None, cache=None, lora=None):
     """All decoder layers of the PREFILL on the flat fp32 stream x [B * S, hidden], in place — ONE C call (stllm_llama_layers).
-    carr = llama_layer_array(layers, cache)."""
+    carr = llama_layer_array(layers, cache).  lora = llama_lora_array(layers): the stack with active adapters (stllm_llama_layers_lora)."""
     _req(x, torch.float32, "x")
     td = torch_dtype(dtype)
     hidden, inter = x.shape[1], layers[0]["wgu"].shape[0] // 2
     L = lib()
     code = stack_dtype_code(td, layers[0]["wdown"])
-    need = int(L.stllm_llama_layers_scratch_bytes(code, B, S, hidden, inter))
+    if lora is not None:
+        need = int(L.stllm_llama_layers_lora_scratch_bytes(code, B, S, hidden, inter, layers[0]["lora_P"]))
+        if need < 0:
+            raise RuntimeError("stllm_llama_layers_lora: bad shape / dtype (bf16x3 runs merged adapters only)")
+    else:
+        need = int(L.stllm_llama_layers_scratch_bytes(code, B, S, hidden, inter))
     scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
     ws = gemm_workspace(x.device)
     cos, sin = rope
@@ -630,6 +680,9 @@ def llama_layers(x, layers, carr, *, B, S, n_heads, eps, rope, dtype, kv_len=Non
         _req(kv_len, torch.int32, "kv_len")
     a = LlamaLayersArgs(code, B, S, n_heads, hidden, inter, float(eps), x.data_ptr(), x.stride(0), cos.data_ptr(), sin.data_ptr(),
                         _p(kv_len), cache.max_len if cache is not None else 0, scratch.data_ptr(), need, ws.data_ptr(), ws.numel())
+    if lora is not None:
+        _check(L.stllm_llama_layers_lora(ctypes.byref(a), carr, lora, len(layers), _stream()), "stllm_llama_layers_lora")
+        return x
     _check(L.stllm_llama_layers(ctypes.byref(a), carr, len(layers), _stream()), "stllm_llama_layers")
     return x
 

@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip, pack, runtime
+from . import lora as lora_mod
 from .layers import Embedding, Linear, Output, ParamList, RMSNorm, params_fingerprint
 
 
@@ -69,7 +70,7 @@ class LlamaDecoderLayer(nn.Module):
         self.input_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, device)
         self.post_attention_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, device)
 
-    def pack(self, dt, n_heads, frag=True):
+    def pack(self, dt, n_heads, frag=True, lora=True):
         a, m = self.self_attn, self.mlp
         pk = dict(ln1=self.input_layernorm.weight, ln2=self.post_attention_layernorm.weight,
                   wqkv=pack.llama_qkv(a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, dt, n_heads),
@@ -81,6 +82,14 @@ class LlamaDecoderLayer(nn.Module):
         # the C entry point and hip.gemm accept one all the same (stllm_llama_layer_weights.wgu_frag, w_frag=)
         pk["wqkv_frag"] = pack.frag32_or_none(pk["wqkv"]) if (frag and dt != torch.float32) else None   # (fp32 / bf16x3: other kernels)
         pk["wgu_frag"] = None
+        ad = lora_mod.adapters_of(self) if lora else None
+        if ad is not None:
+            # active LoRA adapters: the QKV weight gets P extra K columns holding s B (models/lora.py: extend_qkv) and the prefill / decode GEMM runs over
+            # K = hidden + P.  The W-direct kernel needs K % 256 == 0: no fragment-major copy, the dispatcher takes the 128 x 256 one-wave tile instead
+            if runtime.gemm_split():
+                raise NotImplementedError("LoRA adapters in the bf16x3 / mixed modes: merge_adapter() first (the split GEMMs have no K-extended path)")
+            pk["wqkv"], pk["lora_A"], pk["lora_r"], pk["lora_P"] = lora_mod.extend_qkv(pk["wqkv"], ad[0], ad[1], dt, n_heads)
+            pk["wqkv_frag"] = None
         return pk
 
 
@@ -115,19 +124,42 @@ class LlamaModel(nn.Module):
         self._rope = {}
         self._carr = {}   # C-side table of the packed layers (+ the cache it points into): rebuilt when either changes
         self._plist = ParamList(lambda: self.layers.parameters())
+        self._has_lora = False   # LoraLinear modules on q_proj / v_proj (add_lora)
         self.wd_frag = True   # keep fragment-major copies of wqkv / wgu next to the packed weights (W-direct prefill GEMM); the training step switches this off:
                               # its weights change every step and its taped forward does not use the copies
 
     def pack(self, dtype=None):
         dt = hip.torch_dtype(dtype) if dtype is not None else runtime.compute_dtype()
         fp = params_fingerprint(self._plist.get())   # a stale packed copy after p.data.copy_ / .to(device) would run silently
+        fp = fp + (tuple(lora_mod.adapters_of(l) is not None for l in self.layers),) if self._has_lora else fp   # merged / unmerged adapters pack differently
         hit = self._packed.get(dt)
         if hit is None or hit[0] != fp:
             self._packed = {}  # one packed copy at a time (13.5 GB at 7B) ...
             self._carr = {}    # ... including the C-side table, which holds a reference to the list it was built from
-            hit = (fp, [l.pack(dt, self.config.num_attention_heads, frag=self.wd_frag) for l in self.layers])
+            # adapters whose B is all zero (peft's init: a fresh model) add exact zeros: pack — and run — the base path, bit for bit the model without adapters
+            lora = self.lora_active() and lora_mod.any_nonzero_b(self)   # (one device read per pack miss)
+            hit = (fp, [l.pack(dt, self.config.num_attention_heads, frag=self.wd_frag, lora=lora) for l in self.layers])
             self._packed[dt] = hit
         return hit[1]
+
+    def add_lora(self, r, lora_alpha=32):
+        """peft's get_peft_model for target_modules = [q_proj, v_proj] (st_llm.py:165-177): fresh adapters (B = 0) on every decoder layer"""
+        lora_mod.add_adapters(self, r, lora_alpha)
+        self._has_lora = True
+
+    def lora_active(self):
+        return self._has_lora and any(lora_mod.adapters_of(l) is not None for l in self.layers)
+
+    def repack_adapters(self):
+        """after an optimizer step on the adapters alone (the kernels write the masters behind torch's version counters): refresh A and the P extra
+        columns of the packed QKV weights IN PLACE — the frozen base weights (13 GB at 7B) are not cast again, the C-side tables stay valid.
+        A pack made while B was still all zero has no extra columns: that one is dropped and rebuilt once."""
+        for dt, (fp, layers) in list(self._packed.items()):
+            if "lora_A" not in layers[0]:
+                self.repack()
+                return
+            for l, pk in zip(self.layers, layers):
+                lora_mod.refresh_qkv(pk, *lora_mod.adapters_of(l), dt, self.config.num_attention_heads)
 
     def repack(self):
         self._packed = {}
@@ -188,7 +220,12 @@ class LlamaModel(nn.Module):
                 self._carr = {"layers": layers, "carr": hip.llama_layer_array(layers)}
             carr = self._carr["carr"]
         if STACK_ENTRY:
-            hip.llama_layers(x, layers, carr, B=B, S=S, n_heads=H, eps=cfg.rms_norm_eps, rope=(cos, sin), dtype=dt, kv_len=kv_len, cache=cache)
+            kw = {}
+            if "lora_A" in layers[0]:   # active adapters: stllm_llama_layers_lora, still one C call
+                if self._carr.get("lora_of") is not layers:
+                    self._carr.update(lora_of=layers, lora=hip.llama_lora_array(layers))
+                kw["lora"] = self._carr["lora"]
+            hip.llama_layers(x, layers, carr, B=B, S=S, n_heads=H, eps=cfg.rms_norm_eps, rope=(cos, sin), dtype=dt, kv_len=kv_len, cache=cache, **kw)
         else:
             self.prefill_layers_per_op(x, layers, B, S, cos, sin, kv_len, cache, dt)
         h16, h32 = hip.rmsnorm(x, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
@@ -202,7 +239,7 @@ class LlamaModel(nn.Module):
         H = cfg.num_attention_heads
         hd = D // H
         for li_, pk in enumerate(layers):
-            h, _ = hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)
+            h = self.qkv_operand(x, pk, dt) if "lora_A" in pk else hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)[0]
             if cache is None:
                 qkv = hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cos, sin), rope_seq=S, rope_cols=2 * D, **_frag(pk, "wqkv"))
                 strides = None
@@ -219,6 +256,16 @@ class LlamaModel(nn.Module):
             g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, **_frag(pk, "wgu"))
             hip.gemm(g, pk["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
         return x
+
+    def qkv_operand(self, x, pk, dt):
+        """the A operand of a layer's QKV GEMM: RMSNorm(x) in the compute dtype; with active adapters the rows carry P more columns,
+        t = h [A_q ; A_v]^T and a zero pad (stllm_lora_down), matching the K-extended weight"""
+        cfg = self.config
+        M, D = x.shape
+        buf = torch.empty((M, D + pk["lora_P"]), device=x.device, dtype=dt)
+        hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt, out_t=buf[:, :D])
+        hip.lora_down(buf[:, :D], pk["lora_A"], dtype=dt, out=buf[:, D:])
+        return buf
 
     def sp_layer_part(self, part, x, layers, li, qkv, s0, s1, cos_l, sin_l, dt, carr):
         """one half of a decoder layer on this rank's rows [s0, s1) (prefill_sp): part 0 = RMSNorm + QKV GEMM + RoPE into qkv[s0:s1], part 1 = attention over
@@ -255,6 +302,8 @@ class LlamaModel(nn.Module):
         from .. import parallel
         cfg = self.config
         dt = runtime.compute_dtype()
+        if self.lora_active():
+            raise NotImplementedError("sequence-parallel prefill with active LoRA adapters: merge_adapter() first")
         layers = self.pack(dt)
         B, S, D = inputs_embeds.shape
         if B != 1:
@@ -322,7 +371,9 @@ class LlamaModel(nn.Module):
         fuse = dt != torch.float32 and B <= FUSE_NORM_ROWS
         for li_, pk in enumerate(layers):
             row = cache.qkv[li_][:, pos]                                   # [B, 3D] view, row stride max_len*3D
-            if fuse:
+            if "lora_A" in pk:   # active adapters: the fused-RMSNorm GEMV cannot see t = h A^T — norm, down projection, then the GEMV over K = D + P
+                hip.gemm(self.qkv_operand(x, pk, dt), pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=1, rope_cols=2 * D, out=row)
+            elif fuse:
                 hip.gemm(None, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=1, rope_cols=2 * D, out=row,
                          a_norm=(x, pk["ln1"], cfg.rms_norm_eps))
             else:

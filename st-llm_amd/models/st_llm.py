@@ -667,6 +667,46 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
     def get_model(self):
         return self.model
 
+    # ---- LoRA adapters on q_proj / v_proj (models/lora.py) ------------------------------------------------------------------------
+    def add_lora(self, r, lora_alpha=32):
+        self.model.add_lora(r, lora_alpha)
+        self.config.lora_r, self.config.lora_alpha = r, lora_alpha
+        return self
+
+    def _lora_modules(self):
+        from . import lora
+        return [m for l in self.model.layers for m in (l.self_attn.q_proj, l.self_attn.v_proj) if isinstance(m, lora.LoraLinear)]
+
+    @torch.no_grad()
+    def merge_adapter(self):
+        """peft's merge_adapter: W <- W + s B A on the fp32 masters (on the device, the library's fp32 GEMM); the model then runs the unchanged base path"""
+        for m in self._lora_modules():
+            if not m.merged:
+                m.merge(1.0)
+                m.merged = True
+        self.model.repack()
+
+    @torch.no_grad()
+    def unmerge_adapter(self):
+        for m in self._lora_modules():
+            if m.merged:
+                m.merge(-1.0)
+                m.merged = False
+        self.model.repack()
+
+    def merge_and_unload(self):
+        """peft's merge_and_unload: merge, then drop the adapter modules — a plain model with HF parameter names"""
+        from . import lora
+        self.merge_adapter()
+        lora.unload_adapters(self.model)
+        self.model._has_lora = False
+        return self
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """accepts peft's layout (`base_model.model.` prefix, `base_layer`), HF's, and adapter-only files (strict=False) — models/lora.py: remap_keys"""
+        from . import lora
+        return super().load_state_dict(lora.remap_keys(state_dict, lora.has_adapters(self.model)), strict=strict, **kw)
+
     def resize_token_embeddings(self, n):
         """st_llm.py:180-181 (`model.resize_token_embeddings(model.config.vocab_size)`): both tables to n rows."""
         self.model.resize_token_embeddings(n)
@@ -817,9 +857,9 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
                                       ("hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads",
                                        "vocab_size", "rms_norm_eps", "max_position_embeddings")})
             sd = cls.get_state_dict(llama_model)
-        if cfg.get("lora_r", 0) > 0:
-            raise NotImplementedError("LoRA (peft) is not on the hot path: no shipped config sets lora_r")
         model = cls(lcfg, device=device)
+        if cfg.get("lora_r", 0) > 0:   # st_llm.py:165-177: LoraConfig(r, lora_alpha, target_modules=["q_proj", "v_proj"], lora_dropout=0.05, bias="none")
+            model.add_lora(cfg.get("lora_r"), cfg.get("lora_alpha", 32))
         if sd:
             model.load_state_dict(sd, strict=False)
         model.get_model().initialize_vision_modules(cfg, device=device)
@@ -829,6 +869,8 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
         if ckpt_path and os.path.exists(ckpt_path):
             ckpt = cls.get_state_dict(ckpt_path) if os.path.isdir(ckpt_path) else torch.load(ckpt_path, map_location="cpu")
             ckpt = ckpt.get("model", ckpt)
+            from . import lora
+            ckpt = lora.remap_keys(ckpt, lora.has_adapters(model.model))   # peft's `base_model.model.` prefix goes BEFORE the renames and the vocabulary check
             if "llm_proj.weight" in ckpt:
                 ckpt["llama_proj.weight"] = ckpt.pop("llm_proj.weight")
                 ckpt["llama_proj.bias"] = ckpt.pop("llm_proj.bias")

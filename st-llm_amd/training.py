@@ -90,11 +90,31 @@ class LlamaTape:
         self.cos = self.sin = None
 
 
-def llama_forward_taped(lm, inputs_embeds, attention_mask=None):
-    """LlamaModel.prefill (models/llama.py) with every activation kept.  Returns (h32 [B,S,D], h16 [B*S,D], tape)."""
+def _lora_layer(lm, li, dt):
+    """the unmerged adapters of decoder layer li for the training step: dict(q, v, r, P, A [2 r, D] in dt) or None"""
+    from .models import lora as lora_mod
+    ad = lora_mod.adapters_of(lm.layers[li]) if getattr(lm, "_has_lora", False) else None
+    if ad is None:
+        return None
+    q, v = ad
+    return dict(q=q, v=v, r=q.r, P=hip.lora_pad(q.r, dt), A=torch.cat((q.A.detach(), v.A.detach()), dim=0).to(dt).contiguous())
+
+
+def llama_forward_taped(lm, inputs_embeds, attention_mask=None, lora_dropout=None):
+    """LlamaModel.prefill (models/llama.py) with every activation kept.  Returns (h32 [B,S,D], h16 [B*S,D], tape).
+    lora_dropout: None (no dropout: the deterministic step) or the injected train-mode masks of peft's lora_dropout, a tensor
+    [n_layers, 2 (q_proj, v_proj), B * S, D] of factors (0 or 1 / keep) applied to the adapters' input only."""
+    old_frag = lm.wd_frag
+    lm.wd_frag = False   # (the weights are re-packed after every optimizer step: no second, fragment-major copy of wqkv / wgu for kernels this path does not call)
+    try:
+        return _llama_forward_taped(lm, inputs_embeds, attention_mask, lora_dropout)
+    finally:
+        lm.wd_frag = old_frag   # (ADVICE r06: the switch used to leak into the inference path of the same model)
+
+
+def _llama_forward_taped(lm, inputs_embeds, attention_mask, lora_dropout):
     cfg = lm.config
     dt = runtime.compute_dtype()
-    lm.wd_frag = False   # (the weights are re-packed after every optimizer step: no second, fragment-major copy of wqkv / wgu for kernels this path does not call)
     packs = lm.pack(dt)
     B, S, D = inputs_embeds.shape
     H = cfg.num_attention_heads
@@ -102,6 +122,7 @@ def llama_forward_taped(lm, inputs_embeds, attention_mask=None):
     dev = inputs_embeds.device
     t = LlamaTape()
     t.B, t.S = B, S
+    t.lora_dropout = lora_dropout
     x = inputs_embeds.reshape(B * S, D).float().clone()
     if attention_mask is not None:
         m = attention_mask.to("cpu").long()
@@ -110,10 +131,28 @@ def llama_forward_taped(lm, inputs_embeds, attention_mask=None):
         if int(m.sum()) != m.numel():
             t.kv_len = m.sum(dim=1).to(torch.int32).to(dev)
     t.cos, t.sin = lm.rope(S, dev)
-    for pk in packs:
+    for li, pk in enumerate(packs):
         rec = dict(x0=x.clone())
-        rec["h1"], _ = hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)
-        rec["qkv"] = hip.gemm(rec["h1"], pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(t.cos, t.sin), rope_seq=S, rope_cols=2 * D)
+        ad = _lora_layer(lm, li, dt)
+        if ad is None:
+            rec["h1"], _ = hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)
+            a_op = rec["h1"]
+        else:
+            # adapters: h1 and t = h1 [A_q ; A_v]^T in one row buffer (the K-extended operand of the QKV GEMM); t is kept for dB
+            r, P = ad["r"], ad["P"]
+            buf = torch.empty((B * S, D + P), device=dev, dtype=dt)
+            hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt, out_t=buf[:, :D])
+            rec["h1"], rec["t"], rec["buf"] = buf[:, :D], buf[:, D:], buf
+            if lora_dropout is None:
+                hip.lora_down(buf[:, :D], ad["A"], dtype=dt, out=buf[:, D:])
+            else:   # q_proj and v_proj drop their inputs independently: one down projection per mask
+                tmp = torch.empty((B * S, P), device=dev, dtype=dt)
+                rec["hd"] = [(buf[:, :D].float() * lora_dropout[li, j]).to(dt) for j in range(2)]
+                hip.lora_down(rec["hd"][1], ad["A"], dtype=dt, out=buf[:, D:])
+                hip.lora_down(rec["hd"][0], ad["A"], dtype=dt, out=tmp)
+                buf[:, D:D + r] = tmp[:, :r]
+            a_op = buf if "lora_A" in pk else buf[:, :D]   # (adapters whose B is still all zero pack the base weight: t only feeds dB)
+        rec["qkv"] = hip.gemm(a_op, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(t.cos, t.sin), rope_seq=S, rope_cols=2 * D)
         q = rec["qkv"]
         rec["a"] = hip.attention(q[:, :D], q[:, D:2 * D], q[:, 2 * D:], B=B, H=H, Sq=S, Skv=S, D=hd, scale=hd ** -0.5, causal=True,
                                  kv_len=t.kv_len)
@@ -131,6 +170,54 @@ def llama_forward_taped(lm, inputs_embeds, attention_mask=None):
 
 def _no_sink(name):
     return None
+
+
+def _lora_qkv_backward(lm, li, pk, rec, dqkv, dx, dt, grads, a, dropout):
+    """Backward of the adapted QKV projection  qkv = [h1 | t] W'^T,  t = [A_q (m_q h1) ; A_v (m_v h1)]  (m = 1 without dropout):
+        dt = dqkv[:, q | v] · s B      (the extra K columns of the transposed extended weight: one GEMM with dh1's base part)
+        dB = s · dqkv^T t              (q rows un-permuted as unpack_qkv_grad does)
+        dA = dt^T (m h1),   dh1 += m (dt · A)
+    The base weight is frozen: no [3 D, D] weight gradient.  Accumulates dL/dx0 into dx, returns d(input_layernorm.weight)."""
+    cfg = lm.config
+    ad = _lora_layer(lm, li, dt)
+    q, v, r, P = ad["q"], ad["v"], ad["r"], ad["P"]
+    D = cfg.hidden_size
+    H = cfg.num_attention_heads
+    kg = _kgran(dt)
+    # dB: (t^T dqkv) = [P, 3 D] — the skinny operand is the GEMM's row side (N = 3 D columns)
+    dext = hip.gemm(hip.transpose(rec["t"].contiguous(), pad=kg), hip.transpose(dqkv, pad=kg), dtype=dt, out_f32=True)   # [P, 3 D]
+    perm = pack.rope_head_perm(H, D // H, dqkv.device)
+    dBq = torch.empty((D, r), device=dqkv.device, dtype=torch.float32)
+    dBq[perm] = dext[:r, :D].t() * q.scaling
+    grads[a + "q_proj.lora_B.default.weight"] = dBq
+    grads[a + "v_proj.lora_B.default.weight"] = (dext[r:2 * r, 2 * D:].t() * v.scaling).contiguous()
+    if "lora_A" in pk:
+        wt = hip.transpose(pk["wqkv"], pad=kg)                                       # [D + P, 3 D]: base rows, then the s B rows
+        dh1 = hip.gemm(dqkv, wt[:D], dtype=dt)                                       # the base part of dL/dh1
+        wx = torch.zeros((128, wt.shape[1]), device=wt.device, dtype=dt)            # dt = dqkv · (s B): N = P padded to the GEMMs' 128 columns
+        wx[:P] = wt[D:D + P]
+        dtl = hip.gemm(dqkv, wx, dtype=dt)[:, :P].contiguous()
+    else:   # B == 0: dt == 0, the adapters pass no gradient to A or h1 yet
+        dh1, _ = linear_bwd(dqkv, rec["h1"], pk["wqkv"], dt, need_dw=False)
+        dtl = None
+    dgam = hip.rmsnorm_bwd(rec["x0"], pk["ln1"], cfg.rms_norm_eps, dh1, dx, accumulate=True)
+    dA = torch.zeros((2 * r, D), device=dqkv.device, dtype=torch.float32)
+    if dtl is not None:
+        dtt = hip.transpose(dtl, pad=kg)                                            # [P, Mp]
+        if dropout is None:
+            dA = hip.gemm(dtt, hip.transpose(rec["h1"].contiguous(), pad=kg), dtype=dt, out_f32=True)[:2 * r]
+            At = torch.zeros((D, P), device=dqkv.device, dtype=dt)
+            At[:, :2 * r] = ad["A"].t()
+            dgam = dgam + hip.rmsnorm_bwd(rec["x0"], pk["ln1"], cfg.rms_norm_eps, hip.gemm(dtl, At, dtype=dt), dx, accumulate=True)
+        else:
+            for j in range(2):
+                dA[j * r:(j + 1) * r] = hip.gemm(dtt, hip.transpose(rec["hd"][j], pad=kg), dtype=dt, out_f32=True)[j * r:(j + 1) * r]
+                At = torch.zeros((D, P), device=dqkv.device, dtype=dt)
+                At[:, j * r:(j + 1) * r] = ad["A"][j * r:(j + 1) * r].t()
+                dh = (hip.gemm(dtl, At, dtype=dt, out_f32=True) * dropout[li, j]).to(dt)
+                dgam = dgam + hip.rmsnorm_bwd(rec["x0"], pk["ln1"], cfg.rms_norm_eps, dh, dx, accumulate=True)
+    grads[a + "q_proj.lora_A.default.weight"], grads[a + "v_proj.lora_A.default.weight"] = dA[:r].contiguous(), dA[r:2 * r].contiguous()
+    return dgam
 
 
 def llama_backward(lm, tape, d_h16=None, d_h32=None, prefix="model.", sink=_no_sink):
@@ -157,30 +244,36 @@ def llama_backward(lm, tape, d_h16=None, d_h32=None, prefix="model.", sink=_no_s
             d = hip.rmsnorm_bwd(tape.x_final, lm.norm.weight, cfg.rms_norm_eps, dy, dx, accumulate=True)
             dgam = d if dgam is None else dgam + d
     grads[prefix + "norm.weight"] = dgam
+    # with adapters the base Llama weights are frozen (st_llm.py:182-185 keeps the 'lora' parameters only): no weight-gradient GEMMs for them
+    wg = not (getattr(lm, "_has_lora", False) and lm.lora_active())
     # ---- layers, last to first ---------------------------------------------------------------------------------------
     for li in range(len(packs) - 1, -1, -1):
         pk, rec = packs[li], tape.layers[li]
         lp = f"{prefix}layers.{li}."
         dx16 = hip.cast_rows(dx, dt)
         # x2 = x1 + g @ Wdown^T
-        dg, dw = linear_bwd(dx16, rec["g"], pk["wdown"], dt, dw_out=sink(lp + "mlp.down_proj.weight"))
+        dg, dw = linear_bwd(dx16, rec["g"], pk["wdown"], dt, dw_out=sink(lp + "mlp.down_proj.weight"), need_dw=wg)
         grads[lp + "mlp.down_proj.weight"] = dw
         dgu = hip.swiglu_bwd(rec["gu"], dg)
-        dh2, dw = linear_bwd(dgu, rec["h2"], pk["wgu"], dt)
-        grads[lp + "mlp.gate_proj.weight"], grads[lp + "mlp.up_proj.weight"] = unpack_gate_up_grad(
-            dw, (sink(lp + "mlp.gate_proj.weight"), sink(lp + "mlp.up_proj.weight")))
+        dh2, dw = linear_bwd(dgu, rec["h2"], pk["wgu"], dt, need_dw=wg)
+        if wg:
+            grads[lp + "mlp.gate_proj.weight"], grads[lp + "mlp.up_proj.weight"] = unpack_gate_up_grad(
+                dw, (sink(lp + "mlp.gate_proj.weight"), sink(lp + "mlp.up_proj.weight")))
         grads[lp + "post_attention_layernorm.weight"] = hip.rmsnorm_bwd(rec["x1"], pk["ln2"], cfg.rms_norm_eps, dh2, dx, accumulate=True)
         # x1 = x0 + a @ Wo^T          (dx is now dL/dx1)
         dx16 = hip.cast_rows(dx, dt)
-        da, dw = linear_bwd(dx16, rec["a"], pk["wo"], dt, dw_out=sink(lp + "self_attn.o_proj.weight"))
+        da, dw = linear_bwd(dx16, rec["a"], pk["wo"], dt, dw_out=sink(lp + "self_attn.o_proj.weight"), need_dw=wg)
         grads[lp + "self_attn.o_proj.weight"] = dw
         qkv = rec["qkv"]
         dqkv = torch.empty_like(qkv)
         hip.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], rec["a"], da, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:],
                           B=B, H=H, S=S, D=hd, scale=hd ** -0.5, causal=True, kv_len=tape.kv_len)
         hip.rope_bwd(dqkv, tape.cos, tape.sin, rope_seq=S, rope_cols=2 * D)
-        dh1, dw = linear_bwd(dqkv, rec["h1"], pk["wqkv"], dt)
         a = lp + "self_attn."
+        if "t" in rec:
+            grads[lp + "input_layernorm.weight"] = _lora_qkv_backward(lm, li, pk, rec, dqkv, dx, dt, grads, a, tape.lora_dropout)
+            continue
+        dh1, dw = linear_bwd(dqkv, rec["h1"], pk["wqkv"], dt)
         grads[a + "q_proj.weight"], grads[a + "k_proj.weight"], grads[a + "v_proj.weight"] = unpack_qkv_grad(
             dw, H, (sink(a + "q_proj.weight"), sink(a + "k_proj.weight"), sink(a + "v_proj.weight")))
         grads[lp + "input_layernorm.weight"] = hip.rmsnorm_bwd(rec["x0"], pk["ln1"], cfg.rms_norm_eps, dh1, dx, accumulate=True)
@@ -198,7 +291,7 @@ def _mark(name):
         PHASES.append((name, ev))
 
 
-def loss_and_grads(model, samples, freeze_btadapter=False, drop_path=None, sink=None):
+def loss_and_grads(model, samples, freeze_btadapter=False, drop_path=None, sink=None, lora_dropout=None):
     """model: STLLMForCausalLM.  Returns (loss fp32 scalar tensor, loss_mvm or None, grads {reference name: fp32 tensor}).
     sink: AdamW.grad_sink() — the LLM's weight gradients (lm_head, 32 x q/k/v/o/gate/up/down, the embedding table) are then produced IN the
     optimizer's flat gradient buffer and the returned tensors alias it (train_step does this); None: every gradient is its own tensor.
@@ -228,7 +321,7 @@ def loss_and_grads(model, samples, freeze_btadapter=False, drop_path=None, sink=
     B, S, _ = inputs_embeds.shape
     dev = inputs_embeds.device
     _mark("vision forward + assembly")
-    h32, h16, lt = llama_forward_taped(lm, inputs_embeds, attention_mask)
+    h32, h16, lt = llama_forward_taped(lm, inputs_embeds, attention_mask, lora_dropout=lora_dropout)   # lora_dropout: see llama_forward_taped
     _mark("LLM forward")
     grads = {}
     # ---- shifted CE (st_llm.py:125-135) ---------------------------------------------------------------------------
@@ -347,8 +440,12 @@ def trainable_parameters(model, freeze_btadapter=False):
     frozen = ("model.stllm_model.visual_encoder", "model.stllm_model.ln_vision", "model.stllm_model.Qformer",
               "model.stllm_model.query_tokens")
     seen = set()
+    # with LoRA adapters the reference freezes the language model except the adapters (st_llm.py:182-185: `'lora' in name` stays trainable)
+    lora = getattr(model.model, "_has_lora", False)
     for n, prm in model.named_parameters():
         if (n.startswith(frozen) and ("BTAdapter" not in n or freeze_btadapter)) or id(prm) in seen:
+            continue
+        if lora and "lora_" not in n and not n.startswith("model.stllm_model."):
             continue
         seen.add(id(prm))
         yield n, prm
@@ -507,10 +604,10 @@ def trainable_state_dict(model):
     return {n: p.detach().clone() for n, p in trainable_parameters(model)}
 
 
-def train_step(model, samples, optimizer, freeze_btadapter=False, drop_path=None):
+def train_step(model, samples, optimizer, freeze_btadapter=False, drop_path=None, lora_dropout=None):
     """One optimisation step (HF Trainer.training_step + optimizer.step for gradient_accumulation_steps = 1).  Returns (loss, loss_mvm, gradient norm) —
     deliberately NOT the gradients: the LLM's weight gradients live in the optimizer's flat buffer (AdamW.grad_sink) and are consumed by the step."""
-    loss, loss_mvm, grads = loss_and_grads(model, samples, freeze_btadapter, drop_path, sink=optimizer.grad_sink())
+    loss, loss_mvm, grads = loss_and_grads(model, samples, freeze_btadapter, drop_path, sink=optimizer.grad_sink(), lora_dropout=lora_dropout)
     norm = optimizer.step(grads)
     invalidate_packed(model)
     if loss.is_cuda:   # optimizer.step() read the gradient norm back: the stream is idle, check the split-K exchanges of this step
@@ -521,8 +618,11 @@ def train_step(model, samples, optimizer, freeze_btadapter=False, drop_path=None
 def invalidate_packed(model):
     """drop the cached compute-dtype copies of the TRAINABLE parameters (re-packed lazily from the updated masters; the kernels
     update the masters behind torch's version counters).  The frozen ViT / Q-Former copies stay."""
-    model._lm_packed = {}
-    model.model.repack()
+    if getattr(model.model, "_has_lora", False) and model.model.lora_active():
+        model.model.repack_adapters()    # the base Llama weights and lm_head are frozen: only A and the s B columns of the packed copies are refreshed
+    else:
+        model._lm_packed = {}
+        model.model.repack()
     sm = model.model.stllm_model
     for name in ("llama_proj", "down_proj", "up_proj"):
         if hasattr(sm, name):
