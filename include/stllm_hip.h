@@ -239,6 +239,13 @@ typedef struct {
 int64_t stllm_llama_layers_scratch_bytes(int dtype, int B, int S, int hidden, int inter);
 /* the decoder-layer loop of the PREFILL (st_llm.py:56-92 -> HF LlamaModel.forward, use_cache False or filling a fresh cache) */
 int stllm_llama_layers(const stllm_llama_layers_args* args, const stllm_llama_layer_weights* layers, int n_layers, void* stream);
+/* the decoder-layer loop for S NEW positions pos0 .. pos0 + S - 1 behind pos0 positions already in the KV cache (LlamaModel.extend; additive to ABI 7):
+ * as stllm_llama_layers with a cache (args->cache_max_len >= pos0 + S, args->kv_len NULL, args->rope_cos / rope_sin pointing at position pos0's table row),
+ * but layer l's fused QKV rows go to rows [pos0, pos0 + S) of every batch entry's block of layers[l].kv_cache and the attention is stllm_attention_offset
+ * (Sq = S, Skv = pos0 + S, q_off = pos0) with `attn_workspace` (>= stllm_attention_offset_workspace_bytes(B, n_heads, S, pos0 + S), or NULL: tile kernels only).
+ * Scratch as for stllm_llama_layers.  bf16 / fp16 / fp32.  The same launches, in the same order, as the per-op path: bit-identical. */
+int stllm_llama_layers_extend(const stllm_llama_layers_args* args, const stllm_llama_layer_weights* layers, int n_layers, int pos0,
+                              void* attn_workspace, int64_t attn_workspace_bytes, void* stream);
 /* ---- LoRA adapters on q_proj / v_proj (peft 0.8.1 Linear, eval: y = W x + (lora_alpha / r) B (A x); the reference builds them at st_llm.py:165-177).  Additive to
  * ABI 7: new symbols only, no existing struct changes.
  *
@@ -365,6 +372,23 @@ int stllm_attention(int dtype, const void* q, int64_t q_bs, int64_t q_rs,
                     void* out, int64_t o_bs, int64_t o_rs,
                     int B, int H, int Sq, int Skv, int D, float scale, int causal,
                     const int32_t* kv_len, void* stream);
+
+/*
+ * stllm_attention with a QUERY OFFSET (additive to ABI 7): query row i (0 <= i < Sq) sits at position q_off + i; with `causal`, key j is visible iff
+ * j <= q_off + i.  Needs q_off >= 0 and q_off + Sq <= Skv; q_off = 0 with Sq == Skv is stllm_attention's causal case.  Operand addressing, dtypes and kv_len
+ * as for stllm_attention.  The shape this exists for is a short suffix behind a long KV cache (Sq new rows, Skv = q_off + Sq cached keys): in bf16 / fp16 at
+ * head_dim 128 such shapes run a key-split kernel pair — the keys of one (batch, head, query chunk) are split over several workgroups that leave fp32
+ * partial softmax states in `workspace`, a second launch merges them in a fixed order (deterministic) —, everything else the register-staged tile kernels.
+ * workspace: NULL (tile kernels only) or >= stllm_attention_offset_workspace_bytes(B, H, Sq, Skv) bytes, 16-byte aligned, no initialisation needed.
+ * stllm_set_option("attn_ksplit", 0 / 1 / -1): never / wherever eligible / by the measured rule (default).  stllm_last_kernel() names the kernel that ran.
+ */
+int64_t stllm_attention_offset_workspace_bytes(int B, int H, int Sq, int Skv);
+int stllm_attention_offset(int dtype, const void* q, int64_t q_bs, int64_t q_rs,
+                           const void* k, int64_t k_bs, int64_t k_rs,
+                           const void* v, int64_t v_bs, int64_t v_rs,
+                           void* out, int64_t o_bs, int64_t o_rs,
+                           int B, int H, int Sq, int Skv, int D, float scale, int causal,
+                           const int32_t* kv_len, int q_off, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
  * Row gather (token-block assembly, dynamic masking, residual-index selection, embedding lookup):

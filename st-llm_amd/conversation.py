@@ -23,6 +23,13 @@ class StoppingCriteriaSub:
         return False
 
 
+class VideoPrefix:
+    """the KV cache of a video's tokens (positions 0 .. n_tokens - 1), reusable across questions (Chat.prefill_video)"""
+
+    def __init__(self, cache, n_tokens):
+        self.cache, self.n_tokens = cache, n_tokens
+
+
 class Chat:
     def __init__(self, model, device="cuda:0"):
         self.device = device
@@ -70,11 +77,23 @@ class Chat:
         question = (conv.system if system else "") + "###Human: " + question + " ###Assistant: "
         return self.get_context_emb_ids(img_list, self.model.llama_tokenizer.encode_ids(question, add_special_tokens=False))
 
+    def prefill_video(self, img_list):
+        """Prefill the video tokens img_list[0] ONCE: in the get_context_emb_sim layout they come first (positions 0 .. Nv - 1), so their K / V rows
+        do not depend on the question.  Returns a VideoPrefix (the cache in the current compute dtype) for answer(prefix=...).
+        With a text-conditioned Q-Former (upload_video(text=question)) the video tokens depend on that text: the prefix is then valid for the question
+        it was encoded with only — the caller's responsibility, as img_list already is."""
+        emb = img_list[0]
+        lm = self.LLM.model
+        cache = lm.new_cache(emb.shape[0], emb.shape[1], emb.device)
+        lm.prefill(emb, None, cache=cache)
+        return VideoPrefix(cache, emb.shape[1])
+
     def answer(self, img_list, question_ids, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9,
                repetition_penalty=1.0, length_penalty=1, temperature=1.0, max_length=2000, do_sample=False,
-               stopping_criteria=None, instruction=False, **kw):
+               stopping_criteria=None, instruction=False, prefix=None, **kw):
         """conversation.py:213-253: keep the last `max_length - max_new_tokens` embeddings, generate with the reference's
-        knobs (demo.py: num_beams=5, do_sample=False), drop a leading <unk> (0) / <s> (1) token.  This entry point is the
+        knobs (demo.py: num_beams=5, do_sample=False), drop a leading <unk> (0) / <s> (1) token.  prefix: a prefill_video(img_list) result — the
+        video's K / V rows are reused and only [BOS] + question is run (same ids; see prefill_video for the text-conditioned case).  This entry point is the
         `get_context_emb_sim` path (no conv.instruction: video tokens + question), for which the reference OVERRIDES
         repetition_penalty with 1.5 (conversation.py:219-220) whatever the caller passed; instruction=True keeps the argument."""
         embs, att = self.get_context_emb_ids(img_list, question_ids)
@@ -82,6 +101,10 @@ class Chat:
             repetition_penalty = 1.5
         begin = max(0, embs.shape[1] - (max_length - max_new_tokens))
         embs = embs[:, begin:]
+        if prefix is not None and begin == 0:   # prefix = prefill_video(img_list): only [BOS] + question is new.  begin > 0: the truncation rule
+            assert prefix.n_tokens == img_list[0].shape[1] == prefix.cache.len   # would cut into the cached positions — the whole-prompt path below
+            embs = embs[:, prefix.n_tokens:]
+            kw = dict(kw, prefix_cache=prefix.cache)
         if stopping_criteria is None:
             stopping_criteria = self.stopping_criteria
         out = self.LLM.generate(inputs_embeds=embs, max_new_tokens=max_new_tokens, stopping_criteria=stopping_criteria,

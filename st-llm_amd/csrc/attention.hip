@@ -32,6 +32,10 @@ struct AttnParams {
   const int32_t* kv_len;
   int q_lds;                            // attn_dma_kernel: the query tiles arrive through the LDS (set by launch_dma when they fit)
   int merge_par;                        // attn_dma_kernel, KS2 > 1: every partner wave has its own merge slot (one barrier pair instead of one per partner)
+  // stllm_attention_offset (0 / null through stllm_attention): query row i sits at position q_off + i, so with `causal` key j is visible iff j <= q_off + i.
+  // Read by attn_mfma_kernel, attn_mfma_f32_kernel and attn_f32_kernel only; the LDS-DMA / resident kernels are not reached with an offset.
+  int q_off;
+  float* ws; int nsplit, kps;           // attn_mfma_kernel<.., SPLIT>: partial records, key ranges per query chunk, keys per range (a multiple of 32)
 };
 
 constexpr float kNeg = -1.0e30f;
@@ -62,7 +66,11 @@ __device__ __forceinline__ void attn_block_coords(int& chunk_x, int& h, int& b) 
   b = id / (gx * gy);
 }
 
-template <typename T, int DP, int NW>
+// SPLIT (key-split partial pass of stllm_attention_offset, DP = 128): blockIdx.x = query chunk * nsplit + key range; the workgroup walks the keys
+// [range * kps, (range + 1) * kps) only and leaves the un-normalised fp32 state (O[128], m, l) of every query row in p.ws for attn_ksplit_merge_kernel.
+constexpr int kSplRec = 132;   // floats per partial record: O[128], m (raw-score maximum), l, 2 pad (16-byte aligned records)
+
+template <typename T, int DP, int NW, bool SPLIT = false>
 __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) {
   constexpr int KS = DP / 16;          // k-steps of the S^T MFMA chain
   constexpr int DB = DP / 32;          // 32-row blocks of O^T
@@ -78,7 +86,9 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lh = lane >> 5;
   const int b = blockIdx.z, h = blockIdx.y;
-  const int q_blk0 = blockIdx.x * (32 * NW);
+  const int q_chunk = SPLIT ? (int)blockIdx.x / p.nsplit : (int)blockIdx.x;
+  const int k_range = SPLIT ? (int)blockIdx.x - q_chunk * p.nsplit : 0;
+  const int q_blk0 = q_chunk * (32 * NW);
   const int qrow = q_blk0 + wave * 32 + li;  // this lane's query
   const int D = p.D;
   const int kvlen = p.kv_len ? min(p.kv_len[b], p.Skv) : p.Skv;
@@ -103,7 +113,9 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
   float m_run = kNeg, l_run = 0.0f;
 
   int kv_end = kvlen;
-  if (p.causal) kv_end = min(kv_end, q_blk0 + 32 * NW);  // keys beyond the last query of the block are masked
+  if (p.causal) kv_end = min(kv_end, p.q_off + q_blk0 + 32 * NW);  // keys beyond the last query of the block are masked
+  const int kv_begin = SPLIT ? k_range * p.kps : 0;
+  if (SPLIT) kv_end = min(kv_end, kv_begin + p.kps);
   const char* kbase = p.k + ((int64_t)b * p.k_bs + (int64_t)h * D) * 2;
   const char* vbase = p.v + ((int64_t)b * p.v_bs + (int64_t)h * D) * 2;
 
@@ -122,9 +134,9 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
       vreg[c] = ok ? *reinterpret_cast<const i32x4*>(vbase + ((int64_t)kv * p.v_rs + cc * 8) * 2) : z;
     }
   };
-  const int wave_q_last = q_blk0 + wave * 32 + 31;  // last query row of this wave (causal tile skipping)
-  if (kv_end > 0) load_tile(0);
-  for (int kv0 = 0; kv0 < kv_end; kv0 += 32) {
+  const int wave_q_last = p.q_off + q_blk0 + wave * 32 + 31;  // position of the last query row of this wave (causal tile skipping)
+  if (kv_end > kv_begin) load_tile(kv_begin);
+  for (int kv0 = kv_begin; kv0 < kv_end; kv0 += 32) {
     __syncthreads();  // previous tile fully consumed
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
@@ -154,12 +166,12 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
       s = Elem<T>::mfma(kf, qf[ks], s);
     }
     // ---- mask + online softmax (per-lane query); scores stay RAW, the scale is folded into the exp2 argument ----
-    const bool need_mask = (kv0 + 32 > kvlen) || (p.causal && kv0 + 31 > q_blk0 + wave * 32);  // wave-uniform
+    const bool need_mask = (kv0 + 32 > kvlen) || (p.causal && kv0 + 31 > p.q_off + q_blk0 + wave * 32);  // wave-uniform
     if (need_mask) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int kv = kv0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const bool dead = (kv >= kvlen) || (p.causal && kv > qrow);
+        const bool dead = (kv >= kvlen) || (p.causal && kv > qrow + p.q_off);
         s[r] = dead ? kNeg : s[r];
       }
     }
@@ -207,6 +219,25 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
   }
 
   // ---- normalise and store: lane holds O[q][d = i*32 + (r&3) + 8*(r>>2) + 4*lh] ------------------------
+  if constexpr (SPLIT) {
+    static_assert(!SPLIT || DP == 128, "the partial records hold 128 dims");
+    if (qrow < p.Sq) {
+      // a row that saw no key of this range (its tiles skipped, or every key of them masked) has m_run == kNeg and, where a tile was walked for the
+      // sake of the wave's other rows, exp2(0) weights in l / O: its record is the empty state, which the merge weighs with exactly 0
+      const bool empty = m_run <= 0.5f * kNeg;
+      float* rec = p.ws + ((((int64_t)b * p.H + h) * p.Sq + qrow) * p.nsplit + k_range) * kSplRec;
+#pragma unroll
+      for (int i = 0; i < DB; ++i)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const f32x4 ov = {o[i][4 * g + 0], o[i][4 * g + 1], o[i][4 * g + 2], o[i][4 * g + 3]};
+          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+          *reinterpret_cast<f32x4*>(rec + i * 32 + 8 * g + 4 * lh) = empty ? z : ov;
+        }
+      if (lh == 0) { rec[128] = empty ? kNeg : m_run; rec[129] = empty ? 0.0f : l_run; }
+    }
+    return;
+  }
   if (qrow < p.Sq) {
     const float inv = 1.0f / l_run;
     uint16_t* op = reinterpret_cast<uint16_t*>(p.o) + (int64_t)b * p.o_bs + (int64_t)qrow * p.o_rs + (int64_t)h * D;
@@ -1001,7 +1032,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnParams p) {
   if (qrow >= p.Sq) return;  // no block-level sync below
   const int D = p.D;
   const int kvlen = p.kv_len ? min(p.kv_len[b], p.Skv) : p.Skv;
-  const int kv_end = p.causal ? min(kvlen, qrow + 1) : kvlen;
+  const int kv_end = p.causal ? min(kvlen, p.q_off + qrow + 1) : kvlen;
   const float* q = reinterpret_cast<const float*>(p.q) + (int64_t)b * p.q_bs + (int64_t)qrow * p.q_rs + (int64_t)h * D;
   const float* kb = reinterpret_cast<const float*>(p.k) + (int64_t)b * p.k_bs + (int64_t)h * D;
   const float* vb = reinterpret_cast<const float*>(p.v) + (int64_t)b * p.v_bs + (int64_t)h * D;
@@ -1086,7 +1117,7 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_f32_kernel(const AttnParams
   float m_run = kNeg, l_run = 0.0f;
 
   int kv_end = kvlen;
-  if (p.causal) kv_end = min(kv_end, q_blk0 + 32 * NW);
+  if (p.causal) kv_end = min(kv_end, p.q_off + q_blk0 + 32 * NW);
   const float* kbase = reinterpret_cast<const float*>(p.k) + (int64_t)b * p.k_bs + (int64_t)h * D;
   const float* vbase = reinterpret_cast<const float*>(p.v) + (int64_t)b * p.v_bs + (int64_t)h * D;
   f32x4 kreg[CPT], vreg[CPT];
@@ -1102,7 +1133,7 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_f32_kernel(const AttnParams
       vreg[c] = ok ? *reinterpret_cast<const f32x4*>(vbase + (int64_t)kv * p.v_rs + cc * 4) : z;
     }
   };
-  const int wave_q_last = q_blk0 + wave * 32 + 31;
+  const int wave_q_last = p.q_off + q_blk0 + wave * 32 + 31;
   if (kv_end > 0) load_tile(0);
   for (int kv0 = 0; kv0 < kv_end; kv0 += 32) {
     __syncthreads();
@@ -1129,12 +1160,12 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_f32_kernel(const AttnParams
 #pragma unroll
       for (int e = 0; e < 4; ++e) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qf[ks][e], s, 0, 0, 0);
     }
-    const bool need_mask = (kv0 + 32 > kvlen) || (p.causal && kv0 + 31 > q_blk0 + wave * 32);
+    const bool need_mask = (kv0 + 32 > kvlen) || (p.causal && kv0 + 31 > p.q_off + q_blk0 + wave * 32);
     if (need_mask) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int kv = kv0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const bool dead = (kv >= kvlen) || (p.causal && kv > qrow);
+        const bool dead = (kv >= kvlen) || (p.causal && kv > qrow + p.q_off);
         s[r] = dead ? kNeg : s[r];
       }
     }
@@ -1491,6 +1522,144 @@ extern "C" int stllm_attention(int dtype, const void* q, int64_t q_bs, int64_t q
   return STLLM_ERR_BAD_DTYPE;
 }
 
+
+// =====================================================================================================
+// Attention with a query offset (a suffix of Sq positions appended behind q_off cached ones: LlamaModel.extend).
+//   tile path: attn_mfma_kernel / attn_mfma_f32_kernel / attn_f32_kernel with AttnParams.q_off in their causal predicates and tile bounds;
+//   key-split path (16-bit, D = 128): few query tiles against many keys is 32 heads x 1-3 query tiles = a few dozen workgroups, each walking
+//     every key tile serially.  The keys of one (batch, head, query chunk) are split into `nsplit` ranges of whole 32-key tiles; one workgroup
+//     of attn_mfma_kernel<.., SPLIT> per range leaves (O, m, l) per query row in the workspace, attn_ksplit_merge_kernel combines the ranges in
+//     ascending order (deterministic) and writes the compute-dtype rows.  Two launches, no flags, no polling.
+// =====================================================================================================
+namespace {
+
+template <typename T>
+__global__ __launch_bounds__(64) void attn_ksplit_merge_kernel(const AttnParams p) {
+  const int lane = threadIdx.x, qrow = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const float* rec = p.ws + (((int64_t)b * p.H + h) * p.Sq + qrow) * p.nsplit * kSplRec;
+  float mm = kNeg;
+  for (int s = 0; s < p.nsplit; ++s) mm = fmaxf(mm, rec[s * kSplRec + 128]);
+  float ll = 0.0f, a0 = 0.0f, a1 = 0.0f;
+  for (int s = 0; s < p.nsplit; ++s) {
+    const float f = __builtin_amdgcn_exp2f((rec[s * kSplRec + 128] - mm) * p.scale_log2);   // empty ranges: exp2(-huge) == 0
+    ll = fmaf(rec[s * kSplRec + 129], f, ll);
+    a0 = fmaf(rec[s * kSplRec + 2 * lane], f, a0);
+    a1 = fmaf(rec[s * kSplRec + 2 * lane + 1], f, a1);
+  }
+  const float inv = 1.0f / ll;
+  uint32_t* op = reinterpret_cast<uint32_t*>(p.o + ((int64_t)b * p.o_bs + (int64_t)qrow * p.o_rs + (int64_t)h * 128 + 2 * lane) * 2);
+  *op = Elem<T>::pack2(a0 * inv, a1 * inv);
+}
+
+// waves (= 32-row query tiles) per workgroup and key ranges per query chunk of the key-split path: a pure function of the shape, shared by the
+// workspace query and the launch.  Ranges are whole 32-key tiles, at least two tiles each, at most 16 ranges; enough of them for ~512 workgroups.
+struct KsplitPlan { int nw, chunks, nsplit, kps; };
+KsplitPlan ksplit_plan(int B, int H, int Sq, int Skv) {
+  KsplitPlan pl;
+  const int q_tiles = (Sq + 31) / 32;
+  pl.nw = q_tiles < 4 ? q_tiles : 4;
+  pl.chunks = (q_tiles + pl.nw - 1) / pl.nw;
+  const int tiles = (Skv + 31) / 32;
+  const int64_t wgs = (int64_t)B * H * pl.chunks;
+  int want = (int)((512 + wgs - 1) / wgs);
+  if (want > 16) want = 16;
+  if (want > tiles / 2) want = tiles / 2;
+  if (want < 1) want = 1;
+  const int tps = (tiles + want - 1) / want;
+  pl.kps = tps * 32;
+  pl.nsplit = (tiles + tps - 1) / tps;
+  return pl;
+}
+
+template <typename T, int NW>
+void launch_ksplit_nw(const AttnParams& p, const KsplitPlan& pl, hipStream_t stream) {
+  hipLaunchKernelGGL((attn_mfma_kernel<T, 128, NW, true>), dim3(pl.chunks * pl.nsplit, p.H, p.B), dim3(64 * NW), 0, stream, p);
+}
+
+template <typename T>
+int launch_ksplit(AttnParams p, hipStream_t stream) {
+  const KsplitPlan pl = ksplit_plan(p.B, p.H, p.Sq, p.Skv);
+  p.nsplit = pl.nsplit;
+  p.kps = pl.kps;
+  switch (pl.nw) {
+    case 1: launch_ksplit_nw<T, 1>(p, pl, stream); break;
+    case 2: launch_ksplit_nw<T, 2>(p, pl, stream); break;
+    case 3: launch_ksplit_nw<T, 3>(p, pl, stream); break;
+    default: launch_ksplit_nw<T, 4>(p, pl, stream); break;
+  }
+  hipLaunchKernelGGL(attn_ksplit_merge_kernel<T>, dim3(p.Sq, p.H, p.B), dim3(64), 0, stream, p);
+  STLLM_CHECK_LAUNCH("stllm_attention_offset(key split)");
+  stllm_set_last_kernel("attn_ksplit_kernel");
+  return STLLM_OK;
+}
+
+// the dispatch rule of the key-split path.  stllm_set_option("attn_ksplit", 1 / 0) forces it on (wherever it is eligible) / off.
+// tools/attn_bench.py --suffix (MI355X, bf16, 32 heads, graph replays, us tile -> key split; profiles/prefix_cache.md): Sq = 8: 38 -> 14 / 69 -> 18 / 142 -> 26 at
+// q_off = 512 / 1024 / 2048; Sq = 40: 38 -> 17 / 68 -> 23 / 137 -> 27 (q_off = 128: 15 -> 12, 256: 23 -> 13); Sq = 96: 40 -> 21 / 70 -> 31 / 142 -> 40;
+// Sq = 200 behind 1024: 83 -> 34; Sq = 320 behind 2048: 155 -> 73; five beams' worth (B = 5, Sq = 40 behind 1024): 75 -> 52.  It won on every shape measured, so the
+// rule is the measured region: up to 320 (batch, head, query tile) triples and at least 160 keys.  Larger problems fill the chip with query tiles alone and were
+// not measured: they stay on the tile kernel.
+bool ksplit_wins(const AttnParams& p) {
+  const int q_tiles = (p.Sq + 31) / 32;
+  return (int64_t)p.B * p.H * q_tiles <= 320 && p.Skv >= 160;
+}
+
+template <typename T>
+int dispatch_offset(const AttnParams& p, hipStream_t stream) {
+  const int opt = stllm_options().attn_ksplit;
+  if (p.D == 128 && p.ws && opt != 0 && (opt > 0 || ksplit_wins(p))) return launch_ksplit<T>(p, stream);
+  stllm_set_last_kernel("attn_mfma_kernel");
+  const int nw = p.Sq <= 32 ? 1 : (p.Sq <= 64 ? 2 : 3);
+  if (p.D == 128) return nw == 1 ? launch_mfma<T, 128, 1>(p, stream) : nw == 2 ? launch_mfma<T, 128, 2>(p, stream) : launch_mfma<T, 128, 3>(p, stream);
+  if (p.D == 88) return nw == 1 ? launch_mfma<T, 96, 1>(p, stream) : launch_mfma<T, 96, 3>(p, stream);
+  return nw == 1 ? launch_mfma<T, 64, 1>(p, stream) : launch_mfma<T, 64, 2>(p, stream);
+}
+
+}  // namespace
+
+extern "C" int64_t stllm_attention_offset_workspace_bytes(int B, int H, int Sq, int Skv) {
+  if (B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0) return -1;
+  return (int64_t)B * H * Sq * ksplit_plan(B, H, Sq, Skv).nsplit * kSplRec * 4;
+}
+
+extern "C" int stllm_attention_offset(int dtype, const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs,
+                                      int64_t k_rs, const void* v, int64_t v_bs, int64_t v_rs, void* out, int64_t o_bs,
+                                      int64_t o_rs, int B, int H, int Sq, int Skv, int D, float scale, int causal,
+                                      const int32_t* kv_len, int q_off, void* workspace, int64_t workspace_bytes, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  STLLM_CHECK_ARG(q && k && v && out, "stllm_attention_offset: null pointer");
+  STLLM_CHECK_ARG(B > 0 && H > 0 && Sq > 0 && Skv > 0, "stllm_attention_offset: empty problem");
+  STLLM_CHECK_ARG(D == 64 || D == 88 || D == 128, "stllm_attention_offset: head_dim %d not in {64,88,128}", D);
+  STLLM_CHECK_ARG(q_off >= 0 && (int64_t)q_off + Sq <= Skv, "stllm_attention_offset: needs 0 <= q_off and q_off + Sq <= Skv (q_off %d, Sq %d, Skv %d)", q_off, Sq, Skv);
+  STLLM_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out), "stllm_attention_offset: pointers must be 16-byte aligned");
+  STLLM_CHECK_ARG(q_rs % 8 == 0 && k_rs % 8 == 0 && v_rs % 8 == 0 && o_rs % 8 == 0 && q_bs % 8 == 0 && k_bs % 8 == 0 &&
+                      v_bs % 8 == 0 && o_bs % 8 == 0, "stllm_attention_offset: strides must be multiples of 8 elements");
+  AttnParams p{};
+  p.q = (const char*)q; p.q_bs = q_bs; p.q_rs = q_rs;
+  p.k = (const char*)k; p.k_bs = k_bs; p.k_rs = k_rs;
+  p.v = (const char*)v; p.v_bs = v_bs; p.v_rs = v_rs;
+  p.o = (char*)out; p.o_bs = o_bs; p.o_rs = o_rs;
+  p.B = B; p.H = H; p.Sq = Sq; p.Skv = Skv; p.D = D;
+  p.scale = scale; p.scale_log2 = scale * 1.44269504088896340736f;
+  p.causal = causal; p.kv_len = kv_len;
+  p.q_off = causal ? q_off : 0;   // without the causal mask the offset has no effect
+  // the key-split path needs its workspace; a call without one (or with too small a one) runs the tile kernels
+  if (workspace && aligned16(workspace) && workspace_bytes >= stllm_attention_offset_workspace_bytes(B, H, Sq, Skv)) p.ws = reinterpret_cast<float*>(workspace);
+  switch (dtype) {
+    case STLLM_BF16: return dispatch_offset<bf16_t>(p, stream);
+    case STLLM_F16: return dispatch_offset<f16_t>(p, stream);
+    case STLLM_F32:
+      // the vector kernel keeps a row's scores in LDS (Skv <= 2048) and is the one-row kernel: longer caches run the matrix-core kernel at any Sq
+      if (Skv > kF32MaxKv && D == 128 && (Sq < 8 || stllm_options().attn_f32_mfma == 0)) {
+        stllm_set_last_kernel("attn_mfma_f32_kernel");
+        return launch_mfma_f32<128, 1>(p, stream);
+      }
+      stllm_set_last_kernel(stllm_options().attn_f32_mfma != 0 && Sq >= 8 ? "attn_mfma_f32_kernel" : "attn_f32_kernel");
+      return dispatch_f32(p, stream, stllm_options().attn_f32_mfma);
+  }
+  stllm_set_error("stllm_attention_offset: bad dtype %d", dtype);
+  return STLLM_ERR_BAD_DTYPE;
+}
 
 extern "C" int64_t stllm_attention_decode_workspace_bytes(int B, int H, int Skv) {
   if (B <= 0 || H <= 0 || Skv <= 0) return -1;

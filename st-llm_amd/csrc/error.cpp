@@ -50,6 +50,7 @@ StllmOptions& stllm_options() {
     o.gemm_w4_odd = env_int("STLLM_GEMM_W4_ODD", 1);
     o.gemm_w4_wide = env_int("STLLM_GEMM_W4_WIDE", 1);
     o.attn_f32_mfma = env_int("STLLM_ATTN_F32_MFMA", 1);
+    o.attn_ksplit = env_int("STLLM_ATTN_KSPLIT", -1);
     init = true;
   }
   return o;
@@ -74,6 +75,7 @@ extern "C" int stllm_set_option(const char* key, int value) {
   if (!strcmp(key, "gemm_w4_odd")) { o.gemm_w4_odd = value; return STLLM_OK; }
   if (!strcmp(key, "gemm_w4_wide")) { o.gemm_w4_wide = value; return STLLM_OK; }
   if (!strcmp(key, "attn_f32_mfma")) { o.attn_f32_mfma = value; return STLLM_OK; }
+  if (!strcmp(key, "attn_ksplit")) { o.attn_ksplit = value; return STLLM_OK; }
   stllm_set_error("stllm_set_option: unknown key %s", key);
   return STLLM_ERR_UNSUPPORTED;
 }

@@ -17,5 +17,6 @@ struct StllmOptions {
   int gemm_wd;             // STLLM_GEMM_WD: -1 auto | 0 off | 4 / 6 force the W-direct kernel (gemm_wd.inc) with that many 32-row fragments per tile wherever it is eligible
   int attn_q_lds;          // STLLM_ATTN_Q_LDS: 1 (default) the LDS-DMA attention kernels stage their query tiles through the LDS (row-contiguous requests, one copy per tile) | 0 per-lane fragment loads from global memory (rounds 2-5)
   int norm_fast;           // STLLM_NORM_FAST: 1 (default) one row per wave | 2 two rows per wave for >= 2048 short rows (bit-identical; measured equal: 22.36 / 22.47 / 22.41 / 22.40 ms per step)
+  int attn_ksplit;         // STLLM_ATTN_KSPLIT: -1 (default) stllm_attention_offset takes the key-split kernel pair where its rule says it wins | 0 never | 1 wherever it is eligible (16-bit, head_dim 128, a workspace)
 };
 StllmOptions& stllm_options();

@@ -155,7 +155,10 @@ extern "C" int64_t stllm_llama_layers_scratch_bytes(int dtype, int B, int S, int
 // lora == nullptr: the base stack.  Otherwise (stllm_llama_layers_lora) layer l's QKV GEMM runs on the K-extended operands: the RMSNorm writes h into rows
 // of D + P columns, stllm_lora_down puts t = h [A_q ; A_v]^T (+ zero pad) behind it, and ONE GEMM of K = D + P over lora[l].wqkv_ext adds s B t in the
 // fp32 accumulator before the RoPE epilogue.  Everything after the QKV rows is the base stack's.
-static int llama_layers_impl(const stllm_llama_layers_args* a, const stllm_llama_layer_weights* layers, const stllm_llama_lora_layer* lora, int n_layers, void* stream) {
+// pos0 >= 0 (stllm_llama_layers_extend): the S rows are the positions pos0 .. pos0 + S - 1 behind pos0 rows already in the cache — the QKV rows land at
+// row pos0 of every batch entry's cache block and the attention is stllm_attention_offset over the pos0 + S cached keys.  pos0 < 0: the prefill.
+static int llama_layers_impl(const stllm_llama_layers_args* a, const stllm_llama_layer_weights* layers, const stllm_llama_lora_layer* lora, int n_layers, void* stream,
+                             int pos0 = -1, void* attn_ws = nullptr, int64_t attn_ws_bytes = 0) {
   if (!a || (!layers && n_layers > 0) || n_layers < 0) { stllm_set_error("stllm_llama_layers: null arguments"); return STLLM_ERR_BAD_SHAPE; }
   if (!dtype_ok(a->dtype)) { stllm_set_error("stllm_llama_layers: bad dtype %d", a->dtype); return STLLM_ERR_BAD_DTYPE; }
   if (a->n_heads <= 0 || a->hidden <= 0 || a->inter <= 0 || a->B <= 0 || a->S <= 0 || a->hidden % a->n_heads != 0 || a->ldx < a->hidden ||
@@ -184,6 +187,10 @@ static int llama_layers_impl(const stllm_llama_layers_args* a, const stllm_llama
   const int64_t ldh = x3 ? 3 * (int64_t)D : D + P, ldg = x3 ? 3 * (int64_t)a->inter : a->inter;
   if (a->cache_max_len != 0 && (a->cache_max_len < a->S || a->kv_len != nullptr)) {
     stllm_set_error("stllm_llama_layers: the KV cache needs max_len >= S and equal-length sequences");
+    return STLLM_ERR_BAD_SHAPE;
+  }
+  if (pos0 >= 0 && (a->cache_max_len < (int64_t)pos0 + a->S || x3)) {
+    stllm_set_error("stllm_llama_layers_extend: needs a KV cache with max_len >= pos0 + S (%d + %d, max_len %lld) and a bf16 / fp16 / fp32 dtype", pos0, a->S, (long long)a->cache_max_len);
     return STLLM_ERR_BAD_SHAPE;
   }
   Carver c(a->scratch, a->scratch_bytes);
@@ -226,11 +233,19 @@ static int llama_layers_impl(const stllm_llama_layers_args* a, const stllm_llama
       bs = a->cache_max_len * 3 * D;
       g.o_rows_per_batch = a->S; g.o_batch_stride = bs;
     }
-    g.out = qkv;
-    STACK_TRY(stllm_gemm(&g, stream));
     const int64_t rs = 3 * D;
-    STACK_TRY(stllm_attention(adt, qkv, bs, rs, qkv + (int64_t)D * e, bs, rs, qkv + (int64_t)2 * D * e, bs, rs, att,
-                              (int64_t)a->S * D, D, a->B, a->n_heads, a->S, a->S, hd, scale, 1, a->kv_len, stream));
+    if (pos0 >= 0) {
+      char* q_new = qkv + (int64_t)pos0 * rs * e;
+      g.out = q_new;
+      STACK_TRY(stllm_gemm(&g, stream));
+      STACK_TRY(stllm_attention_offset(adt, q_new, bs, rs, qkv + (int64_t)D * e, bs, rs, qkv + (int64_t)2 * D * e, bs, rs, att, (int64_t)a->S * D, D,
+                                       a->B, a->n_heads, a->S, pos0 + a->S, hd, scale, 1, nullptr, pos0, attn_ws, attn_ws_bytes, stream));
+    } else {
+      g.out = qkv;
+      STACK_TRY(stllm_gemm(&g, stream));
+      STACK_TRY(stllm_attention(adt, qkv, bs, rs, qkv + (int64_t)D * e, bs, rs, qkv + (int64_t)2 * D * e, bs, rs, att,
+                                (int64_t)a->S * D, D, a->B, a->n_heads, a->S, a->S, hd, scale, 1, a->kv_len, stream));
+    }
     g = gemm_base(a->dtype, a->workspace, a->workspace_bytes, sws, sws_bytes);
     g.epilogue = STLLM_EPI_RESID; g.A = att; g.lda = D; g.W = w.wo; g.ldw = w.ld_o;
     g.out = a->x; g.ldo = a->ldx; g.resid = a->x; g.ldr = a->ldx; g.M = M; g.N = D; g.K = D;
@@ -253,6 +268,12 @@ static int llama_layers_impl(const stllm_llama_layers_args* a, const stllm_llama
 
 extern "C" int stllm_llama_layers(const stllm_llama_layers_args* a, const stllm_llama_layer_weights* layers, int n_layers, void* stream) {
   return llama_layers_impl(a, layers, nullptr, n_layers, stream);
+}
+
+extern "C" int stllm_llama_layers_extend(const stllm_llama_layers_args* a, const stllm_llama_layer_weights* layers, int n_layers, int pos0,
+                                         void* attn_workspace, int64_t attn_workspace_bytes, void* stream) {
+  if (pos0 < 0 || !a || a->cache_max_len == 0) { stllm_set_error("stllm_llama_layers_extend: needs pos0 >= 0 and a KV cache"); return STLLM_ERR_BAD_SHAPE; }
+  return llama_layers_impl(a, layers, nullptr, n_layers, stream, pos0, attn_workspace, attn_workspace_bytes);
 }
 
 extern "C" int64_t stllm_llama_layers_lora_scratch_bytes(int dtype, int B, int S, int hidden, int inter, int P) {

@@ -84,13 +84,25 @@ def _stop(stopping_criteria, ids, scores):
 class _CacheStepper:
     """next-token logits from the model: prefill once, then one decode step per token; rows can be re-ordered (beams)."""
 
-    def __init__(self, lm_wrapper, inputs_embeds, rows, max_new_tokens, use_cache=True):
+    def __init__(self, lm_wrapper, inputs_embeds, rows, max_new_tokens, use_cache=True, prefix=None):
         self.m, self.lm = lm_wrapper, lm_wrapper.model
         self.use_cache = use_cache
         emb = inputs_embeds.float()
         B, S, _ = emb.shape
         self.rep = rows // B                      # beams per prompt
-        if use_cache:
+        if prefix is not None:
+            # `prefix`: a KVCache holding the prompt's first positions (a prefilled video); inputs_embeds is the rest.  The work happens on a fork
+            # — a copy of the prefix rows, made once per beam —, so the prefix itself stays as it was and serves the next call.
+            if not use_cache or prefix.batch != B:
+                raise ValueError("generate(prefix=...): needs use_cache and one prefix row per prompt")
+            self.cache = prefix.fork(max_len=prefix.len + S + max_new_tokens)
+            _, h16 = self.lm.extend(emb, self.cache)
+            logits = self.m.logits_from(h16.view(B, S, -1)[:, -1].contiguous(), B, 1)[:, 0]
+            if self.rep > 1:
+                self.cache = self.cache.fork(rows=rows)
+                logits = logits.repeat_interleave(self.rep, dim=0)
+            self.logits = logits.float()
+        elif use_cache:
             self.cache = self.lm.new_cache(B, S + max_new_tokens, emb.device)
             _, h16 = self.lm.prefill(emb, None, cache=self.cache)
             logits = self.m.logits_from(h16.view(B, S, -1)[:, -1].contiguous(), B, 1)[:, 0]
@@ -127,12 +139,14 @@ class _CacheStepper:
 @torch.no_grad()
 def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sample=False, min_length=0, top_p=1.0,
              temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, stopping_criteria=None, eos_token_id=2,
-             pad_token_id=0, use_cache=True, generator=None):
-    """Returns the generated ids [B, n] (the prompt has no ids), HF semantics as described in the module docstring."""
+             pad_token_id=0, use_cache=True, generator=None, prefix=None):
+    """Returns the generated ids [B, n] (the prompt has no ids), HF semantics as described in the module docstring.
+    prefix: a KVCache that already holds the first positions of every prompt (LlamaModel.prefill(cache=...) / Chat.prefill_video); `inputs_embeds` is then
+    the remainder of the prompt, appended behind it in one pass (LlamaModel.extend).  The prefix is left unchanged."""
     B = inputs_embeds.shape[0]
     dev = inputs_embeds.device
     if num_beams == 1:
-        st = _CacheStepper(lm_wrapper, inputs_embeds, B, max_new_tokens, use_cache)
+        st = _CacheStepper(lm_wrapper, inputs_embeds, B, max_new_tokens, use_cache, prefix)
         ids = torch.zeros((B, 0), dtype=torch.long, device=dev)
         unfinished = torch.ones(B, dtype=torch.long, device=dev)
         while True:
@@ -156,7 +170,7 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
     if do_sample:
         raise NotImplementedError("beam-sample is not used by the reference (demo: num_beams=5, do_sample=False)")
     nb = num_beams
-    st = _CacheStepper(lm_wrapper, inputs_embeds, B * nb, max_new_tokens, use_cache)
+    st = _CacheStepper(lm_wrapper, inputs_embeds, B * nb, max_new_tokens, use_cache, prefix)
     ids = torch.zeros((B * nb, 0), dtype=torch.long, device=dev)
     beam_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
     beam_scores[:, 1:] = -1e9

@@ -26,7 +26,8 @@ EXPORTS = ["stllm_last_error", "stllm_abi_version", "stllm_last_kernel", "stllm_
            "stllm_attention_decode", "stllm_gemm_profile", "stllm_gemm_profile_count", "stllm_gemm_profile_read",
            "stllm_vit_blocks_scratch_bytes", "stllm_vit_blocks", "stllm_llama_layers_scratch_bytes", "stllm_llama_layers", "stllm_llama_layer_sp_scratch_bytes", "stllm_llama_layer_sp",
            "stllm_qformer_layers_scratch_bytes", "stllm_qformer_layers", "stllm_split3_rows", "stllm_gemm_split_ws_bytes",
-           "stllm_lora_down_workspace_bytes", "stllm_lora_down", "stllm_llama_layers_lora_scratch_bytes", "stllm_llama_layers_lora"]
+           "stllm_lora_down_workspace_bytes", "stllm_lora_down", "stllm_llama_layers_lora_scratch_bytes", "stllm_llama_layers_lora",
+           "stllm_attention_offset_workspace_bytes", "stllm_attention_offset", "stllm_llama_layers_extend"]
 
 
 def torch_dtype(d):
@@ -160,6 +161,9 @@ def _bind(L, strict=True):
     B("stllm_lora_down", [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_llama_layers_lora_scratch_bytes", [c_int] * 6, c_int64)
     B("stllm_llama_layers_lora", [ctypes.POINTER(LlamaLayersArgs), ctypes.POINTER(LlamaLayerWeights), ctypes.POINTER(LlamaLoraLayer), c_int, c_void_p])
+    B("stllm_attention_offset_workspace_bytes", [c_int] * 4, c_int64)
+    B("stllm_attention_offset", [c_int] + [c_void_p, c_int64, c_int64] * 4 + [c_int] * 5 + [c_float, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p])
+    B("stllm_llama_layers_extend", [ctypes.POINTER(LlamaLayersArgs), ctypes.POINTER(LlamaLayerWeights), c_int, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_gemm_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     B("stllm_gemm_w4_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     return L
@@ -687,6 +691,27 @@ def llama_layers(x, layers, carr, *, B, S, n_heads, eps, rope, dtype, kv_len=Non
     return x
 
 
+def llama_layers_extend(x, layers, carr, *, B, S, pos0, n_heads, eps, rope, dtype, cache):
+    """All decoder layers for S new positions behind the pos0 positions `cache` already holds, on the flat fp32 stream x [B * S, hidden], in place — ONE C call
+    (stllm_llama_layers_extend).  carr = llama_layer_array(layers, cache); rope = (cos, sin) rows of the positions pos0 .. pos0 + S - 1."""
+    _req(x, torch.float32, "x")
+    td = torch_dtype(dtype)
+    hidden, inter = x.shape[1], layers[0]["wgu"].shape[0] // 2
+    L = lib()
+    code = dtype_code(td)
+    need = int(L.stllm_llama_layers_scratch_bytes(code, B, S, hidden, inter))
+    scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = gemm_workspace(x.device)
+    cos, sin = rope
+    _req(cos, torch.float32, "rope cos"); _req(sin, torch.float32, "rope sin")
+    aws = attention_offset_workspace(B, n_heads, S, pos0 + S, x.device) if td != torch.float32 and hidden // n_heads == 128 else None
+    a = LlamaLayersArgs(code, B, S, n_heads, hidden, inter, float(eps), x.data_ptr(), x.stride(0), cos.data_ptr(), sin.data_ptr(),
+                        None, cache.max_len, scratch.data_ptr(), need, ws.data_ptr(), ws.numel())
+    _check(L.stllm_llama_layers_extend(ctypes.byref(a), carr, len(layers), pos0, _p(aws), aws.numel() if aws is not None else 0, _stream()),
+           "stllm_llama_layers_extend")
+    return x
+
+
 def llama_layer_sp(x, carr, li, qkv, *, s0, s1, part, n_heads, eps, rope, dtype, inter):
     """ONE decoder layer of the sequence-parallel prefill, part 0 (RMSNorm + QKV GEMM + RoPE into rows [s0, s1) of `qkv`) or part 1 (attention over the s1
     rows, o_proj, RMSNorm, gate/up, down) — one C call each (stllm_llama_layer_sp).  x f32 [s1 - s0, hidden] in place; carr = llama_layer_array(layers);
@@ -812,11 +837,34 @@ def rmsnorm(x, gamma, eps, *, dtype, out_t=None, out_f32=None, want_t=True, want
 _decode_attn = True   # tests flip this to compare the split-KV decode kernel with the tile kernels
 
 
+def attention_offset_workspace(B, H, Sq, Skv, device):
+    """the partial-state buffer of stllm_attention_offset's key-split kernels (no initialisation needed)"""
+    need = int(lib().stllm_attention_offset_workspace_bytes(B, H, Sq, Skv))
+    if need < 0:
+        raise RuntimeError(f"stllm_attention_offset_workspace_bytes: bad shape (B={B}, H={H}, Sq={Sq}, Skv={Skv})")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
 def attention(q, k, v, *, B, H, Sq, Skv, D, scale, causal=False, kv_len=None, out=None,
-              q_strides=None, k_strides=None, v_strides=None):
+              q_strides=None, k_strides=None, v_strides=None, q_off=0):
     """q/k/v: 2-D views [B*S, >=H*D] of the compute dtype (may be column slices of a fused QKV buffer).
-    *_strides = (batch_stride, row_stride) in elements; default: rows of one batch are consecutive."""
+    *_strides = (batch_stride, row_stride) in elements; default: rows of one batch are consecutive.
+    q_off > 0 (stllm_attention_offset): query row i sits at position q_off + i — with `causal`, key j is visible iff j <= q_off + i (q_off + Sq <= Skv);
+    q_off = 0 is the call it always was."""
     td = q.dtype
+    if q_off:
+        qs = q_strides if q_strides is not None else (Sq * q.stride(0), q.stride(0))
+        ks = k_strides if k_strides is not None else (Skv * k.stride(0), k.stride(0))
+        vs = v_strides if v_strides is not None else (Skv * v.stride(0), v.stride(0))
+        if out is None:
+            out = torch.empty((B * Sq, H * D), device=q.device, dtype=td)
+        if kv_len is not None:
+            _req(kv_len, torch.int32, "kv_len")
+        ws = attention_offset_workspace(B, H, Sq, Skv, q.device) if td != torch.float32 and D == 128 else None
+        _check(lib().stllm_attention_offset(dtype_code(td), _p(q), qs[0], qs[1], _p(k), ks[0], ks[1], _p(v), vs[0], vs[1],
+                                            _p(out), Sq * out.stride(0), out.stride(0), B, H, Sq, Skv, D, scale, int(causal),
+                                            _p(kv_len), int(q_off), _p(ws), ws.numel() if ws is not None else 0, _stream()), "stllm_attention_offset")
+        return out
 
     def st(t, S, given):
         return given if given is not None else (S * t.stride(0), t.stride(0))

@@ -106,6 +106,24 @@ class KVCache:
         self.qkv = [torch.empty((batch, max_len, 3 * hidden), device=device, dtype=dtype) for _ in range(n_layers)]
         self.len = 0
 
+    def fork(self, rows=None, max_len=None):
+        """a new cache holding copies of the first `len` positions, every source row repeated rows // batch times (the beams of a prompt; a
+        reusable prefix that generation must not write behind).  max_len defaults to this cache's."""
+        rows = self.batch if rows is None else rows
+        max_len = self.max_len if max_len is None else max_len
+        assert rows % self.batch == 0 and max_len >= self.len
+        new = KVCache(len(self.qkv), rows, max_len, self.hidden, self.qkv[0].dtype, self.qkv[0].device)
+        n, rep = self.len, rows // self.batch
+        for dst, src in zip(new.qkv, self.qkv):
+            dst[:, :n] = src[:, :n].repeat_interleave(rep, dim=0) if rep > 1 else src[:, :n]
+        new.len = n
+        return new
+
+    def truncate(self, n):
+        """forget the positions from n on (their rows are simply overwritten by the next extend / decode_step)"""
+        assert 0 <= n <= self.len
+        self.len = n
+
 
 STACK_ENTRY = os.environ.get("STLLM_STACK_ENTRY", "1") != "0"   # 0: one C-ABI call per op instead of stllm_llama_layers / stllm_vit_blocks (A/B, tests)
 FUSE_NORM_ROWS = int(os.environ.get("STLLM_DECODE_FUSE_ROWS", "2"))   # decode steps with at most this many rows fuse RMSNorm into the GEMVs
@@ -251,6 +269,58 @@ class LlamaModel(nn.Module):
             a = hip.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B=B, H=H, Sq=S, Skv=S, D=hd,
                               scale=hd ** -0.5, causal=True, kv_len=kv_len, q_strides=strides, k_strides=strides,
                               v_strides=strides)
+            hip.gemm(a, pk["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
+            h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
+            g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, **_frag(pk, "wgu"))
+            hip.gemm(g, pk["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
+        return x
+
+    def extend(self, inputs_embeds, cache):
+        """S new positions behind the P = cache.len positions the cache already holds, in ONE pass through the decoder layers (a question behind a
+        prefilled video; forward(past_key_values=...) runs decode_step once per token instead).  inputs_embeds f32 [B,S,D].  Per layer: RMSNorm ->
+        QKV GEMM + RoPE at the positions P .. P+S-1, written into rows [P, P+S) of the layer's cache buffer -> causal attention of the S query rows over
+        the P+S cached keys with the query offset P (hip.attention(q_off=P)) -> o_proj -> MLP.  Sets cache.len = P + S; returns what prefill returns.
+        P = 0 is prefill(cache=cache).  bf16 / fp16 / fp32; the split modes (bf16x3 / mixed) are not wired."""
+        cfg = self.config
+        dt = runtime.compute_dtype()
+        if runtime.gemm_split():
+            raise NotImplementedError("LlamaModel.extend runs in the bf16 / fp16 / fp32 modes; the bf16x3 / mixed modes have no extend path")
+        B, S, D = inputs_embeds.shape
+        P = cache.len
+        assert cache.batch == B and cache.qkv[0].dtype == dt
+        assert P + S <= cache.max_len, "KV cache full"
+        if P == 0:
+            return self.prefill(inputs_embeds, None, cache=cache)
+        layers = self.pack(dt)
+        H = cfg.num_attention_heads
+        x = inputs_embeds.reshape(B * S, D).float().clone()
+        cos, sin = self.rope(cache.max_len, inputs_embeds.device)
+        cos, sin = cos[P:P + S], sin[P:P + S]
+        if STACK_ENTRY and "lora_A" not in layers[0]:
+            hip.llama_layers_extend(x, layers, hip.llama_layer_array(layers, cache), B=B, S=S, pos0=P, n_heads=H, eps=cfg.rms_norm_eps, rope=(cos, sin),
+                                    dtype=dt, cache=cache)
+        else:
+            self.extend_layers_per_op(x, layers, B, S, P, cos, sin, cache, dt)
+        cache.len = P + S
+        h16, h32 = hip.rmsnorm(x, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
+        return h32.view(B, S, D), h16
+
+    def extend_layers_per_op(self, x, layers, B, S, P, cos, sin, cache, dt):
+        """extend's layer loop as one C-ABI call per op — what stllm_llama_layers_extend issues from C (bit-identical), the body active LoRA adapters
+        run, and the one the test-only CPU contract backend runs"""
+        cfg = self.config
+        D = cfg.hidden_size
+        H = cfg.num_attention_heads
+        hd = D // H
+        ML3 = cache.max_len * 3 * D
+        for li_, pk in enumerate(layers):
+            h = self.qkv_operand(x, pk, dt) if "lora_A" in pk else hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)[0]
+            full = cache.qkv[li_].view(B * cache.max_len, 3 * D)
+            new = full[P:]                                         # row (b, s) of the suffix at b * max_len + P + s
+            hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cos, sin), rope_seq=S, rope_cols=2 * D,
+                     out=new, M=B * S, o_rows=(S, ML3), **_frag(pk, "wqkv"))
+            a = hip.attention(new[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=S, Skv=P + S, D=hd, scale=hd ** -0.5, causal=True,
+                              q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D), v_strides=(ML3, 3 * D), q_off=P)
             hip.gemm(a, pk["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
             h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
             g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, **_frag(pk, "wgu"))

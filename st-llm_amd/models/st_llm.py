@@ -787,14 +787,18 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
     @torch.no_grad()
     def generate(self, inputs_embeds=None, max_new_tokens=16, num_beams=1, do_sample=False, stopping_criteria=None,
                  attention_mask=None, use_cache=True, min_length=0, top_p=1.0, repetition_penalty=1.0, length_penalty=1.0,
-                 temperature=1.0, eos_token_id=2, pad_token_id=0, generator=None, **unused):
+                 temperature=1.0, eos_token_id=2, pad_token_id=0, generator=None, prefix_cache=None, **unused):
         """`llama_model.generate(inputs_embeds=..., ...)` as Chat.answer calls it (conversation.py:231-243; demo.py runs
         num_beams=5, do_sample=False): HIP prefill of `inputs_embeds` into a KV cache, then one decode step per token with
         HF's greedy / sampling / beam-search bookkeeping restated in stllm_amd/generation.py.  eos / pad default to the
         Vicuna generation config (2 / 0).  A padded batch (attention_mask rows of different valid lengths, left- or right-padded) is generated by length groups
-        (see below).  Returns the generated ids [B, n] (the prompt has no ids)."""
+        (see below).  Returns the generated ids [B, n] (the prompt has no ids).
+        prefix_cache: a KVCache holding the first positions of the prompt (Chat.prefill_video); `inputs_embeds` is then the rest of the prompt only, and
+        the prefix is left unchanged for the next call.  One prompt x beams, as the reference sends: ragged batches reject it."""
         from .. import generation
         if attention_mask is not None and inputs_embeds.shape[0] > 1:
+            if prefix_cache is not None and not bool(hip.host_mask(attention_mask).to(torch.bool).all()):
+                raise NotImplementedError("generate(prefix_cache=...) with a padded batch: a prefix serves equal-length prompts only")
             # Ragged prompts (round 5).  The device KV cache holds equal-length rows (one position counter, RoPE by row index), and the reference itself only
             # ever sends one prompt x beams (conversation.py:231-243) — so a padded batch is served by LENGTH GROUPS: HF derives position_ids from the mask
             # (positions count real tokens only), i.e. every row generates exactly as its unpadded prompt would alone; rows of equal length share one
@@ -824,7 +828,7 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
                                    min_length=min_length, top_p=top_p, temperature=temperature,
                                    repetition_penalty=repetition_penalty, length_penalty=length_penalty,
                                    stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                                   use_cache=use_cache, generator=generator)
+                                   use_cache=use_cache, generator=generator, prefix=prefix_cache)
 
     @classmethod
     def get_state_dict(cls, path, prefix="pytorch_model"):

@@ -14,6 +14,47 @@ if "--probe" in sys.argv:   # how does the Llama prefill kernel's time scale wit
 AUDIT = "--audit" in sys.argv   # the Llama prefill kernel's work split (query tiles per workgroup x waves per query tile) forced through option attn_dma = 10 nw + ks
 if AUDIT:
     CASES = [(f"llama_S{S}_B{B}", B, 32, S, S, 128, True, 32) for B, S in ((1, 178), (1, 296), (1, 400), (1, 528), (1, 576), (1, 700), (1, 1088), (4, 576), (2, 576), (16, 576))]
+if "--suffix" in sys.argv:
+    # LlamaModel.extend's shape: Sq new rows behind q_off cached ones, operands addressed inside one fused cache buffer as the model passes them.
+    # The offset tile kernel (attn_ksplit = 0) and the key-split pair (1) on the same buffers, same process, alternating; "auto" is the dispatch rule.
+    # Every timing replays a captured graph of 20 calls, so that launch gaps on the host do not hide a difference of a few microseconds.
+    def timed(fn, rounds=5):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(20):
+                fn()
+        g.replay(); torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        best = float("inf")
+        for _ in range(rounds):
+            s.record(); g.replay(); e.record(); torch.cuda.synchronize()
+            best = min(best, s.elapsed_time(e) / 20 * 1e3)
+        return best
+    shapes = [(B, Sq, off) for B in (1,) for Sq in (8, 40, 96) for off in (512, 1024, 2048)] + [(1, 40, 128), (1, 40, 256), (1, 200, 1024), (1, 320, 2048), (5, 40, 1024)]
+    for dt in (torch.bfloat16,) + ((torch.float16,) if "--fp16" in sys.argv else ()):
+        for B, Sq, off in shapes:
+            H, D, Skv = 32, 128, off + Sq
+            ML = Skv + 8
+            buf = torch.randn(B * ML, 3 * H * D, device="cuda").to(dt)
+            st = (ML * 3 * H * D, 3 * H * D)
+            out = torch.empty(B * Sq, H * D, device="cuda", dtype=dt)
+            call = lambda: hip.attention(buf[off:, :H * D], buf[:, H * D:2 * H * D], buf[:, 2 * H * D:], B=B, H=H, Sq=Sq, Skv=Skv, D=D, scale=D ** -0.5, causal=True,
+                                         q_strides=st, k_strides=st, v_strides=st, q_off=off, out=out)
+            res = {}
+            for rnd in range(2):                      # tile, split, tile, split: alternating
+                for opt in (0, 1):
+                    hip.set_option("attn_ksplit", opt)
+                    res.setdefault(opt, []).append(timed(call))
+            hip.set_option("attn_ksplit", -1)
+            call()
+            auto = hip.lib().stllm_last_kernel().decode()
+            t, k = min(res[0]), min(res[1])
+            print(f"suffix {str(dt)[6:]:9s} B={B} Sq={Sq:4d} q_off={off:5d}  tile {t:7.1f} us ({res[0][0]:.1f} {res[0][1]:.1f})  key-split {k:7.1f} us ({res[1][0]:.1f} {res[1][1]:.1f})"
+                  f"  ratio {t / k:5.2f}  auto -> {auto}", flush=True)
+    sys.exit(0)
 for name, B, H, Sq, Skv, D, causal, per_clip in CASES:
     dt = torch.bfloat16
     if Sq == Skv:

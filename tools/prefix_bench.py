@@ -1,0 +1,106 @@
+"""Time per question on a video that is already uploaded, with and without a prefix KV cache (LlamaModel.extend) — one process, one GPU, synthetic
+7B-size Llama weights, greedy decoding of a fixed number of tokens (no EOS), HIP-event / wall timings alternating between the three paths:
+
+  (a) whole prompt   generate(inputs_embeds = video | question): prefill of Nv + Q positions on every question (the path Chat.answer always took)
+  (b) prefix         generate(inputs_embeds = question, prefix_cache = video prefix): fork of the prefix + ONE extend pass over the Q positions
+  (c) per-token      the prefix forked, the question appended by forward(past_key_values=...): one decode_step per question token
+
+"first token" = until the logits of the last prompt position exist; "answer" = first token + max_new_tokens - 1 decode steps (host bookkeeping included).
+Device clock / power over the whole timed region come from bench.py's Telemetry.
+
+    python tools/prefix_bench.py [--layers 32] [--nv 512 2048] [--question 40] [--new 16] [--rounds 5] [--mode bf16]
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--nv", type=int, nargs="+", default=[512, 2048])
+    ap.add_argument("--question", type=int, default=40)
+    ap.add_argument("--new", type=int, default=16)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--mode", default="bf16")
+    a = ap.parse_args()
+    import stllm_amd  # noqa: F401
+    import bench
+    from stllm_amd import runtime, synth
+    from stllm_amd.models.st_llm import STLLMForCausalLM, StllmConfig
+    torch.set_grad_enabled(False)
+    runtime.set_compute_dtype(a.mode)
+    m = STLLMForCausalLM(StllmConfig(num_hidden_layers=a.layers, max_position_embeddings=4096), device="cuda")
+    synth.fill_module_(m, 0, "")
+    lm = m.model
+    Q, N = a.question, a.new
+    q_emb = synth.normal_(torch.empty((1, Q, 4096), device="cuda"), "bench.question", 0, 0.05)
+    kw = dict(max_new_tokens=N, num_beams=1, do_sample=False, eos_token_id=None)
+    tele = bench.Telemetry(0).start()
+    rows = []
+    for nv in a.nv:
+        v_emb = synth.normal_(torch.empty((1, nv, 4096), device="cuda"), f"bench.video{nv}", 0, 0.05)
+        whole = torch.cat([v_emb, q_emb], dim=1)
+        prefix = lm.new_cache(1, nv, "cuda")
+        t_prefill_video = wall(lambda: lm.prefill(v_emb, None, cache=prefix))
+
+        def first_a():
+            c = lm.new_cache(1, nv + Q + N, "cuda")
+            _, h = lm.prefill(whole, None, cache=c)
+            return m.logits_from(h.view(1, nv + Q, -1)[:, -1].contiguous(), 1, 1)
+
+        def first_b():
+            c = prefix.fork(max_len=nv + Q + N)
+            _, h = lm.extend(q_emb, c)
+            return m.logits_from(h.view(1, Q, -1)[:, -1].contiguous(), 1, 1)
+
+        def first_c():
+            c = prefix.fork(max_len=nv + Q + N)
+            o = lm(inputs_embeds=q_emb, past_key_values=c)
+            return m.logits_from(o._h16, 1, 1)
+
+        ans_a = lambda: m.generate(inputs_embeds=whole, **kw)
+        ans_b = lambda: m.generate(inputs_embeds=q_emb, prefix_cache=prefix, **kw)
+        fns = dict(first_a=first_a, first_b=first_b, first_c=first_c, ans_a=ans_a, ans_b=ans_b)
+        ids_a, ids_b = ans_a(), ans_b()                       # warm-up of every path (packing, workspaces, allocator) + a sanity line
+        first_c()
+        same = int((ids_a == ids_b).sum())
+        t = {k: [] for k in fns}
+        for _ in range(a.rounds):                              # alternating: a, b, c, a, b, c, ...
+            for k, fn in fns.items():
+                t[k].append(wall(fn))
+        med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+        best = {k: min(v) for k, v in t.items()}
+        rows.append((nv, t_prefill_video, med, best, same))
+        print(f"[prefix_bench] Nv={nv} Q={Q} new={N}: " + "  ".join(f"{k} {med[k]:.2f} ms (best {best[k]:.2f})" for k in fns) +
+              f"  | prefix ids == whole-prompt ids on {same}/{N} tokens (bf16: summation order differs)", flush=True)
+    telemetry = tele.stop()
+    props = torch.cuda.get_device_properties(0)
+    print(f"\n# Prefix KV cache — {props.name}, {a.layers} layers, {a.mode}, question {Q} tokens, {N} new tokens, greedy, median of {a.rounds} alternating rounds "
+          f"(best in brackets), wall clock around a synchronised call\n")
+    print("| Nv | first token: whole prompt (a) | prefix + extend (b) | prefix + per-token loop (c) | answer: whole prompt (a) | prefix (b) | per-token (c), derived | one-off video prefill |")
+    print("|---|---|---|---|---|---|---|---|")
+    for nv, tv, med, best, same in rows:
+        derived = med["first_c"] + (med["ans_a"] - med["first_a"])
+        print(f"| {nv} | {med['first_a']:.2f} ({best['first_a']:.2f}) | {med['first_b']:.2f} ({best['first_b']:.2f}) | {med['first_c']:.2f} ({best['first_c']:.2f}) | "
+              f"{med['ans_a']:.2f} ({best['ans_a']:.2f}) | {med['ans_b']:.2f} ({best['ans_b']:.2f}) | {derived:.2f} | {tv:.2f} |")
+    print(f"\ntelemetry: {telemetry}")
+    print("(c) answer = its first-token time + the decode steps of (a): the decode loop behind the first token is the same code for all three.")
+
+
+if __name__ == "__main__":
+    main()
