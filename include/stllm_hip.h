@@ -185,6 +185,42 @@ int stllm_gemm_w4_plan(int M, int N, int K, int heavy, int shape, int* plan5);
 int stllm_set_option(const char* key, int value);
 int stllm_gemm(const stllm_gemm_args* args, void* stream);
 
+/*
+ * W8A16 skinny GEMM of the decode regime (st-llm_amd/csrc/gemv.hip), ABI version >= 7 (additive):
+ *   C[M,N] = epilogue(scale[n] * (A[M,K] @ Wq[N,K]^T) + bias[n])
+ * A: bf16 / fp16 [M,lda]; Wq: int8 [N,ldw] (ldw in BYTES = elements), |q| <= 127, packed like the 16-bit weight it was quantised from
+ * (st-llm_amd/pack.py: quant8_rows after llama_qkv / llama_gate_up / linear); scale: f32 [N], one per output row of Wq.
+ * The accumulation is fp32 over the exact products a * q (|q| <= 127 is exact in bf16 and fp16); scale is applied once per output column in
+ * the epilogue, before bias / residual / SwiGLU / RoPE.  Wq and scale are read-only.
+ * Epilogues: STORE (dtype or f32 out, no activation), RESID, SWIGLU, ROPE — the meaning, the (c, c + 32) column pairs, the 2-level row
+ * indexing and the strided output rows of stllm_gemm.  a_norm_*: the fused RMSNorm operand of stllm_gemm_args, M <= 2 only (the VALU kernel).
+ * Kernels: M <= 2 (option "gemv_mfma" = 0: M <= 8) the VALU kernel (v_dot2c on pairs converted in registers; the staged rows of A,
+ * 1 / 2 / 4 / 6 / 8 x K x 2 bytes, must fit 150 KiB of LDS); 3 <= M <= 16 ("gemv_mfma" = 1: from M = 1) the matrix-core kernel (K % 64 == 0).
+ * Constraints: 1 <= M <= 16; N % 64 == 0; K % 16 == 0; Wq 16-byte aligned, ldw % 16 == 0; A / out / resid as for stllm_gemm.
+ * M > 8 (or M >= 3 with the default options) runs on the matrix-core kernel only, which needs K % 64 == 0: K % 64 == 16 / 32 / 48 is served for M <= 8.
+ * A shape or option combination no kernel covers returns STLLM_ERR_UNSUPPORTED (stllm_last_error() says which): nothing else runs in its place.
+ * Launches are seen by stllm_gemm_profile; stllm_last_kernel() names gemv_w8_kernel<...> / gemv_w8_mfma_kernel<...>.
+ * Stands in for the nn.Linear calls of the one-token step (modeling_llama_mem.py:130-144, 163-166) when the weights are held in 8 bits —
+ * the `device_8bit` / low-resource knob of demo.py:41, which the reference carries without an implementation.
+ */
+typedef struct {
+  int dtype;          /* STLLM_BF16 | STLLM_F16: A and the 16-bit outputs */
+  int epilogue;       /* STORE | RESID | SWIGLU | ROPE */
+  int out_is_f32;     /* STORE only */
+  int M, N, K;
+  const void* A; int64_t lda;            /* elements; ignored with a_norm_x */
+  const void* Wq; int64_t ldw;           /* int8 rows, stride in bytes */
+  const float* scale;                    /* f32 [N] */
+  const float* bias;                     /* f32 [N] or NULL */
+  void* out; int64_t ldo;
+  const float* resid; int64_t ldr;
+  const float* rope_cos; const float* rope_sin; int rope_seq; int rope_cols;
+  int a_rows_per_batch; int64_t a_batch_stride;
+  int o_rows_per_batch; int64_t o_batch_stride;
+  const float* a_norm_x; int64_t a_norm_ldx; const float* a_norm_gamma; float a_norm_eps;
+} stllm_gemv_w8_args;
+int stllm_gemv_w8(const stllm_gemv_w8_args* args, void* stream);
+
 /* HIP-event timing of stllm_gemm launches on their launch stream, per calling thread (bench.py's roofline leg; also sees the launches of
  * the whole-stack entry points below).  mode 0 off | 1 every launch | 2 only launches whose kernel symbol — learned per (dtype, epilogue,
  * act, M, N, K) while mode 1 was on — equals target_symbol | 3 every 7th of those (a sample: the event records sit between the kernels on

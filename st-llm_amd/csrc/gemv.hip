@@ -88,34 +88,12 @@ __device__ __forceinline__ void gemv_store(const GemmParams& p, int m, int c0, i
   }
 }
 
-template <typename T, int EPI, int ACT, bool OF32, int MR>
-__global__ __launch_bounds__(256) void gemv_kernel(const GemmParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // A: MR rows x K x 2 bytes
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// Stage the MR rows of A (K x 2 bytes each; 2-level row indexing honoured) in LDS for a 256-thread workgroup; the caller's barrier follows.
+// Shared by the 16-bit VALU kernel and its int8-weight twin (gemv_w8_kernel).
+template <typename T, int MR>
+__device__ __forceinline__ void gemv_stage_a(const GemmParams& p, char* smem, int tid, int lane, int wave) {
   const int K = p.K;
   const int row_bytes = K * 2;
-  // ---- this wave's column pair; its first kU steps of both W rows are requested BEFORE A is staged (the weight stream does not
-  // depend on A: the HBM round trip overlaps the staging — and, with the fused RMSNorm operand, the two passes over x) -------------
-  const int q = blockIdx.x * 4 + wave;           // column-pair index
-  const int c0 = (q >> 5) * 64 + (q & 31), c1 = c0 + 32;
-  const bool active = c0 < p.N;
-  const char* w0 = p.W + (active ? (int64_t)c0 * p.ldw_b : 0);
-  const char* w1 = p.W + (active ? (int64_t)c1 * p.ldw_b : 0);
-  constexpr int kU = 4;                           // steps (1024 bytes of K per wave) per batch; two batches in flight
-  const int lane_b = lane * 16;
-  auto load_batch = [&](i32x4* wa, i32x4* wb, int kbase) {
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int kb = kbase + u * 1024 + lane_b;
-      if (kb < row_bytes) {
-        wa[u] = ldw(w0 + kb);
-        wb[u] = ldw(w1 + kb);
-      }
-    }
-  };
-  i32x4 wa0[kU], wb0[kU], wa1[kU], wb1[kU];
-  load_batch(wa0, wb0, 0);
-  // ---- stage A (2-level row indexing honoured) -------------------------------------------------------------------
   if (p.nx) {
     // A := RMSNorm(x) * gamma, computed here (Llama's input / post-attention norm fused into the projection of the decode step):
     // same arithmetic as norm_row_kernel<T, true> (variance in fp32 over the row, (x * rstd) * gamma, one rounding to T).  Every
@@ -154,6 +132,36 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemmParams p) {
         *reinterpret_cast<i32x4*>(smem + m * row_bytes + c) = *reinterpret_cast<const i32x4*>(src + c);
     }
   }
+}
+
+template <typename T, int EPI, int ACT, bool OF32, int MR>
+__global__ __launch_bounds__(256) void gemv_kernel(const GemmParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // A: MR rows x K x 2 bytes
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = p.K;
+  const int row_bytes = K * 2;
+  // ---- this wave's column pair; its first kU steps of both W rows are requested BEFORE A is staged (the weight stream does not
+  // depend on A: the HBM round trip overlaps the staging — and, with the fused RMSNorm operand, the two passes over x) -------------
+  const int q = blockIdx.x * 4 + wave;           // column-pair index
+  const int c0 = (q >> 5) * 64 + (q & 31), c1 = c0 + 32;
+  const bool active = c0 < p.N;
+  const char* w0 = p.W + (active ? (int64_t)c0 * p.ldw_b : 0);
+  const char* w1 = p.W + (active ? (int64_t)c1 * p.ldw_b : 0);
+  constexpr int kU = 4;                           // steps (1024 bytes of K per wave) per batch; two batches in flight
+  const int lane_b = lane * 16;
+  auto load_batch = [&](i32x4* wa, i32x4* wb, int kbase) {
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int kb = kbase + u * 1024 + lane_b;
+      if (kb < row_bytes) {
+        wa[u] = ldw(w0 + kb);
+        wb[u] = ldw(w1 + kb);
+      }
+    }
+  };
+  i32x4 wa0[kU], wb0[kU], wa1[kU], wb1[kU];
+  load_batch(wa0, wb0, 0);
+  gemv_stage_a<T, MR>(p, smem, tid, lane, wave);
   __syncthreads();
 
   if (!active) return;                            // (no barrier after this point)
@@ -414,6 +422,280 @@ int dispatch_gemv(int epilogue, const GemmParams& p, hipStream_t stream) {
   return STLLM_ERR_UNSUPPORTED;
 }
 
+
+// ---- W8A16: the same two kernels over int8 weights with one fp32 scale per output row (stllm_gemv_w8) -----------------------------
+// The weight stream is half the bytes of the 16-bit kernels above; the integers (|q| <= 127, exact in bf16 and fp16) are widened to
+// 16-bit pairs in registers and meet A on the same v_dot2c / v_mfma_f32_16x16x32 instructions, so the fp32 accumulators hold sums of
+// exact products a * q.  scale[n] multiplies the finished sum once, in the epilogue, before bias / residual / SwiGLU / RoPE.
+__device__ __forceinline__ uint32_t byte_perm(uint32_t s0, uint32_t s1, uint32_t sel) {   // v_perm_b32: selector 0-3 = bytes of s1, 4-7 = bytes of s0
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_perm(s0, s1, sel);
+#else
+  const uint64_t v = ((uint64_t)s0 << 32) | s1;
+  uint32_t r = 0;
+  for (int i = 0; i < 4; ++i) r |= (uint32_t)((v >> (8 * ((sel >> (8 * i)) & 7))) & 0xffu) << (8 * i);
+  return r;
+#endif
+}
+// four int8 of one dword -> two 16-bit pairs (lo = elements 0, 1; hi = elements 2, 3), exactly
+template <typename T> __device__ __forceinline__ void cvt4(uint32_t w, int& lo, int& hi);
+template <> __device__ __forceinline__ void cvt4<bf16_t>(uint32_t w, int& lo, int& hi) {
+  // sign-extending byte -> fp32 conversions; an integer of magnitude <= 127 has 7 significant bits, so the upper half of its fp32 image IS its bf16 image
+  const uint32_t f0 = __builtin_bit_cast(uint32_t, (float)(int8_t)(w & 0xffu)), f1 = __builtin_bit_cast(uint32_t, (float)(int8_t)((w >> 8) & 0xffu));
+  const uint32_t f2 = __builtin_bit_cast(uint32_t, (float)(int8_t)((w >> 16) & 0xffu)), f3 = __builtin_bit_cast(uint32_t, (float)(int8_t)(w >> 24));
+  lo = (int)byte_perm(f1, f0, 0x07060302u);
+  hi = (int)byte_perm(f3, f2, 0x07060302u);
+}
+template <> __device__ __forceinline__ void cvt4<f16_t>(uint32_t w, int& lo, int& hi) {
+  // magic number: fp16 0x6400 | u = 1024 + u has a unit of 1; with u = q + 128 (the byte with its sign bit flipped) 1024 + u - 1152 = q, exactly:
+  // one xor per four weights, one v_perm_b32 and one v_pk_add_f16 per pair
+  const uint32_t x = w ^ 0x80808080u;
+  const gemv_f16x2 off = {(_Float16)1152.0f, (_Float16)1152.0f};
+  lo = __builtin_bit_cast(int, __builtin_bit_cast(gemv_f16x2, byte_perm(0x64646464u, x, 0x04010400u)) - off);
+  hi = __builtin_bit_cast(int, __builtin_bit_cast(gemv_f16x2, byte_perm(0x64646464u, x, 0x04030402u)) - off);
+}
+// 16 int8 -> eight 16-bit pairs in element order
+template <typename T> __device__ __forceinline__ void cvt16(i32x4 w, int* pr) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) cvt4<T>((uint32_t)w[e], pr[2 * e], pr[2 * e + 1]);
+}
+
+// M <= 8 rows on the VALU: gemv_kernel's structure — a wave per column pair (c, c + 32), A staged in LDS behind the first batch of weight loads —
+// with 16 weights per lane, row and step: a wave walks K in 1024-element steps (1 KiB of either W row)
+template <typename T, int EPI, bool OF32, int MR>
+__global__ __launch_bounds__(256) void gemv_w8_kernel(const GemmParams p, const float* __restrict__ scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // A: MR rows x K x 2 bytes
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = p.K;                              // = bytes of one W row
+  const int a_row_bytes = K * 2;
+  const int q = blockIdx.x * 4 + wave;           // column-pair index
+  const int c0 = (q >> 5) * 64 + (q & 31), c1 = c0 + 32;
+  const bool active = c0 < p.N;
+  const char* w0 = p.W + (active ? (int64_t)c0 * p.ldw_b : 0);
+  const char* w1 = p.W + (active ? (int64_t)c1 * p.ldw_b : 0);
+  constexpr int kU = 4;                           // steps per batch; two batches (2 x 8 x 16-byte loads per lane) in flight
+  const int lane_b = lane * 16;
+  auto load_batch = [&](i32x4* wa, i32x4* wb, int kbase) {
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int kb = kbase + u * 1024 + lane_b;
+      if (kb < K) {
+        wa[u] = ldw(w0 + kb);
+        wb[u] = ldw(w1 + kb);
+      }
+    }
+  };
+  i32x4 wa0[kU], wb0[kU], wa1[kU], wb1[kU];
+  load_batch(wa0, wb0, 0);                        // in flight before A is staged
+  gemv_stage_a<T, MR>(p, smem, tid, lane, wave);
+  __syncthreads();
+
+  if (!active) return;                            // (no barrier after this point)
+
+  float acc[MR][2];
+#pragma unroll
+  for (int m = 0; m < MR; ++m) acc[m][0] = acc[m][1] = 0.0f;
+
+  auto fma16 = [&](i32x4 wa, i32x4 wb, int kb) {   // kb = index of this lane's first of 16 elements
+    int pa[8], pb[8];
+    cvt16<T>(wa, pa);
+    cvt16<T>(wb, pb);
+#pragma unroll
+    for (int m = 0; m < MR; ++m) {
+      const i32x4 x0 = *reinterpret_cast<const i32x4*>(smem + m * a_row_bytes + kb * 2);
+      const i32x4 x1 = *reinterpret_cast<const i32x4*>(smem + m * a_row_bytes + kb * 2 + 16);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc[m][0] = dot2_acc<T>(x0[e], pa[e], acc[m][0]);
+        acc[m][1] = dot2_acc<T>(x0[e], pb[e], acc[m][1]);
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc[m][0] = dot2_acc<T>(x1[e], pa[4 + e], acc[m][0]);
+        acc[m][1] = dot2_acc<T>(x1[e], pb[4 + e], acc[m][1]);
+      }
+    }
+  };
+  auto use_batch = [&](const i32x4* wa, const i32x4* wb, int kbase) {
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int kb = kbase + u * 1024 + lane_b;
+      if (kb < K) fma16(wa[u], wb[u], kb);        // ragged last step (K % 1024 != 0): the lanes past the row end sit out
+    }
+  };
+  for (int kbase = 0; kbase < K; kbase += 2 * kU * 1024) {
+    load_batch(wa1, wb1, kbase + kU * 1024);
+    use_batch(wa0, wb0, kbase);
+    load_batch(wa0, wb0, kbase + 2 * kU * 1024);
+    use_batch(wa1, wb1, kbase + kU * 1024);
+  }
+#pragma unroll
+  for (int m = 0; m < MR; ++m) {
+    acc[m][0] = wave_sum(acc[m][0]);
+    acc[m][1] = wave_sum(acc[m][1]);
+  }
+  if (lane != 0) return;
+
+  const float s0 = scale[c0], s1 = scale[c1];
+  const float b0 = p.bias ? p.bias[c0] : 0.0f, b1 = p.bias ? p.bias[c1] : 0.0f;
+  for (int m = 0; m < MR; ++m) {
+    if (m >= p.M) break;
+    gemv_store<T, EPI, STLLM_ACT_NONE, OF32>(p, m, c0, c1, acc[m][0] * s0 + b0, acc[m][1] * s1 + b1);
+  }
+}
+
+// 3 <= M <= 16 rows on the matrix cores: gemv_mfma_kernel's structure (8 waves per 16 columns, or per 2 x 16 partner columns; every wave takes
+// every 8th 64-element k step; partial sums meet in LDS).  Lane l = (column n = l % 16, k-group g = l / 16) loads the 16 weights at bytes
+// [16 g, 16 g + 16) of W row n's 64-byte step — the four k-groups of a row cover one contiguous 64-byte sector — and the 16 elements of A's row at
+// bytes [32 g, 32 g + 32) of its 128-byte step; the two MFMAs of a step take the lower and the upper 8 of those 16.
+template <typename T, int EPI, bool OF32>
+__global__ __launch_bounds__(64 * kGmWaves, 4) void gemv_w8_mfma_kernel(const GemmParams p, const float* __restrict__ scale) {
+  constexpr bool PAIR = (EPI == STLLM_EPI_SWIGLU || EPI == STLLM_EPI_ROPE);
+  constexpr int NL = PAIR ? 4 : 3;              // 16-byte loads per lane and step: 2 of A, 1 or 2 of W
+  __shared__ float red[kGmWaves * (PAIR ? 8 : 4) * 64];   // partial sums of the 8 waves
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n16 = lane & 15, g = lane >> 4;
+  const int unit = blockIdx.x;
+  const int col0 = PAIR ? (unit >> 1) * 64 + (unit & 1) * 16 + n16 : unit * 16 + n16, col1 = col0 + 32;
+  const char* w0 = p.W + (int64_t)col0 * p.ldw_b + g * 16;
+  const char* w1 = p.W + (int64_t)(PAIR ? col1 : col0) * p.ldw_b + g * 16;
+  // A is read straight from global memory (L2 / L1 resident), as in gemv_mfma_kernel; rows >= M of the 16-row operand: any valid row
+  const int am = n16 < p.M ? n16 : p.M - 1;
+  int64_t aoff = (int64_t)am * p.lda_b;
+  if (p.a_rpb > 0) { const int bb = am / p.a_rpb; aoff = (int64_t)bb * p.a_bs_b + (int64_t)(am - bb * p.a_rpb) * p.lda_b; }
+  const char* ax = p.A + aoff + g * 32;
+  const int nsteps = p.K / 64;
+  constexpr int U = 2;                           // steps per batch; two batches in flight
+  i32x4 wq[2][U][NL];
+  // steps past the end of K re-read the last step and meet a zeroed A operand (see gemv_mfma_kernel: no partially valid batches)
+  auto load_batch = [&](int b, int st0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      int st = st0 + kGmWaves * u;
+      st = st < nsteps ? st : nsteps - 1;
+      wq[b][u][0] = *reinterpret_cast<const i32x4*>(ax + st * 128);
+      wq[b][u][1] = *reinterpret_cast<const i32x4*>(ax + st * 128 + 16);
+      wq[b][u][2] = *reinterpret_cast<const i32x4*>(w0 + st * 64);
+      if constexpr (PAIR) wq[b][u][3] = *reinterpret_cast<const i32x4*>(w1 + st * 64);
+    }
+  };
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  auto use_batch = [&](int b, int st0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int keep = (st0 + kGmWaves * u < nsteps) ? -1 : 0;   // wave-uniform mask
+      i32x4 x0 = wq[b][u][0], x1 = wq[b][u][1];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { x0[e] &= keep; x1[e] &= keep; }
+      int pr[8];
+      cvt16<T>(wq[b][u][2], pr);
+      acc0 = mfma16<T>(x0, i32x4{pr[0], pr[1], pr[2], pr[3]}, acc0);
+      acc0 = mfma16<T>(x1, i32x4{pr[4], pr[5], pr[6], pr[7]}, acc0);
+      if constexpr (PAIR) {
+        cvt16<T>(wq[b][u][3], pr);
+        acc1 = mfma16<T>(x0, i32x4{pr[0], pr[1], pr[2], pr[3]}, acc1);
+        acc1 = mfma16<T>(x1, i32x4{pr[4], pr[5], pr[6], pr[7]}, acc1);
+      }
+    }
+  };
+  load_batch(0, wave);
+  for (int st = wave; st < nsteps; st += 2 * U * kGmWaves) {
+    load_batch(1, st + U * kGmWaves);
+    use_batch(0, st);
+    load_batch(0, st + 2 * U * kGmWaves);
+    use_batch(1, st + U * kGmWaves);
+  }
+  constexpr int NR = PAIR ? 8 : 4;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    red[(wave * NR + r) * 64 + lane] = acc0[r];
+    if constexpr (PAIR) red[(wave * NR + 4 + r) * 64 + lane] = acc1[r];
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const float s0 = scale[col0], s1 = PAIR ? scale[col1] : 0.0f;
+  const float b0 = p.bias ? p.bias[col0] : 0.0f, b1 = (PAIR && p.bias) ? p.bias[col1] : 0.0f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int m = 4 * g + r;   // D register r of lane l is D[4 (l / 16) + r][l % 16]
+    float x = 0.0f, y = 0.0f;
+#pragma unroll
+    for (int w = 0; w < kGmWaves; ++w) {   // wave order: deterministic
+      x += red[(w * NR + r) * 64 + lane];
+      if constexpr (PAIR) y += red[(w * NR + 4 + r) * 64 + lane];
+    }
+    if (m < p.M) {
+      if constexpr (PAIR) gemv_store<T, EPI, STLLM_ACT_NONE, OF32>(p, m, col0, col1, x * s0 + b0, y * s1 + b1);
+      else gemv_store1<T, EPI, STLLM_ACT_NONE, OF32>(p, m, col0, x * s0 + b0);
+    }
+  }
+}
+
+const char* w8_kernel_name(char* buf, size_t cap, const char* family, bool bf16, int epi, bool of32, int mr) {
+  static const char* kEpi[] = {"STORE", "RESID", "SWIGLU", "ROPE"};
+  if (mr > 0) snprintf(buf, cap, "%s<%s,%s,%d,%d>", family, bf16 ? "bf16_t" : "f16_t", kEpi[epi], (int)of32, mr);
+  else snprintf(buf, cap, "%s<%s,%s,%d>", family, bf16 ? "bf16_t" : "f16_t", kEpi[epi], (int)of32);
+  return buf;
+}
+
+template <typename T, int EPI, bool OF32>
+int launch_gemv_w8_mfma(const GemmParams& p, const float* scale, hipStream_t stream) {
+  auto kern = gemv_w8_mfma_kernel<T, EPI, OF32>;
+  constexpr bool PAIR = (EPI == STLLM_EPI_SWIGLU || EPI == STLLM_EPI_ROPE);
+  hipLaunchKernelGGL(kern, dim3(p.N / (PAIR ? 32 : 16)), dim3(64 * kGmWaves), 0, stream, p, scale);
+  STLLM_CHECK_LAUNCH("stllm_gemv_w8(mfma)");
+  static char name[96];
+  static const char* named = w8_kernel_name(name, sizeof(name), "gemv_w8_mfma_kernel", std::is_same<T, bf16_t>::value, EPI, OF32, 0);
+  stllm_set_last_kernel(named);
+  return STLLM_OK;
+}
+
+template <typename T, int EPI, bool OF32, int MR>
+int launch_gemv_w8(const GemmParams& p, const float* scale, hipStream_t stream) {
+  auto kern = gemv_w8_kernel<T, EPI, OF32, MR>;
+  const int lds = MR * p.K * 2;
+  static StllmPerDevice lds_dev;   // largest dynamic-LDS size opted into, per device ordinal
+  bool lds_first;
+  const int lds_d = lds_dev.enter(&lds_first);
+  if (lds_first || lds > lds_dev.value[lds_d]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+      stllm_set_error("stllm_gemv_w8: cannot opt into %d bytes of LDS", lds);
+      return STLLM_ERR_UNSUPPORTED;
+    }
+    lds_dev.value[lds_d] = lds;
+    lds_dev.done(lds_d);
+  }
+  hipLaunchKernelGGL(kern, dim3((p.N / 2 + 3) / 4), dim3(256), lds, stream, p, scale);
+  STLLM_CHECK_LAUNCH("stllm_gemv_w8(valu)");
+  static char name[96];
+  static const char* named = w8_kernel_name(name, sizeof(name), "gemv_w8_kernel", std::is_same<T, bf16_t>::value, EPI, OF32, MR);
+  stllm_set_last_kernel(named);
+  return STLLM_OK;
+}
+
+template <typename T, int EPI, bool OF32>
+int launch_gemv_w8_any(const GemmParams& p, const float* scale, bool mfma, hipStream_t stream) {
+  if (mfma) return launch_gemv_w8_mfma<T, EPI, OF32>(p, scale, stream);
+  switch (p.M) {
+    case 1: return launch_gemv_w8<T, EPI, OF32, 1>(p, scale, stream);
+    case 2: return launch_gemv_w8<T, EPI, OF32, 2>(p, scale, stream);
+    case 3: case 4: return launch_gemv_w8<T, EPI, OF32, 4>(p, scale, stream);
+    case 5: case 6: return launch_gemv_w8<T, EPI, OF32, 6>(p, scale, stream);
+    default: return launch_gemv_w8<T, EPI, OF32, 8>(p, scale, stream);   // M = 7, 8
+  }
+}
+
+template <typename T>
+int dispatch_gemv_w8(int epilogue, const GemmParams& p, const float* scale, bool mfma, hipStream_t stream) {
+  switch (epilogue) {
+    case STLLM_EPI_STORE:
+      return p.out_is_f32 ? launch_gemv_w8_any<T, STLLM_EPI_STORE, true>(p, scale, mfma, stream) : launch_gemv_w8_any<T, STLLM_EPI_STORE, false>(p, scale, mfma, stream);
+    case STLLM_EPI_RESID: return launch_gemv_w8_any<T, STLLM_EPI_RESID, false>(p, scale, mfma, stream);
+    case STLLM_EPI_SWIGLU: return launch_gemv_w8_any<T, STLLM_EPI_SWIGLU, false>(p, scale, mfma, stream);
+    default: return launch_gemv_w8_any<T, STLLM_EPI_ROPE, false>(p, scale, mfma, stream);
+  }
+}
+
 }  // namespace
 
 // M <= 16 (the caller decides how far it goes), 16-bit dtypes.  M >= 3 (option "gemv_mfma": 0 never, 1 from M = 1): the matrix-core
@@ -437,4 +719,78 @@ int stllm_gemv_launch(int dtype, int epilogue, const sg::GemmParams& p, hipStrea
   if (dtype == STLLM_BF16) return dispatch_gemv<bf16_t>(epilogue, p, stream);
   if (dtype == STLLM_F16) return dispatch_gemv<f16_t>(epilogue, p, stream);
   return STLLM_ERR_UNSUPPORTED;
+}
+
+int stllm_prof_begin(const stllm_gemm_args* a, void* stream);     // profile.cpp
+void stllm_prof_end(int idx, int rc, const stllm_gemm_args* a, void* stream);
+
+// W8A16 entry point (include/stllm_hip.h).  No fallback: what neither kernel covers is STLLM_ERR_UNSUPPORTED with a message.
+extern "C" int stllm_gemv_w8(const stllm_gemv_w8_args* a, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  STLLM_CHECK_ARG(a != nullptr, "stllm_gemv_w8: null args");
+  if (a->dtype != STLLM_BF16 && a->dtype != STLLM_F16) {
+    stllm_set_error("stllm_gemv_w8: A must be bf16 or fp16 (dtype %d)", a->dtype);
+    return STLLM_ERR_BAD_DTYPE;
+  }
+  STLLM_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "stllm_gemv_w8: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
+  STLLM_CHECK_ARG(a->N % 64 == 0 && a->K % 16 == 0, "stllm_gemv_w8: need N %% 64 == 0 and K %% 16 == 0 (N=%d K=%d)", a->N, a->K);
+  STLLM_CHECK_ARG(a->Wq && aligned16(a->Wq) && a->ldw % 16 == 0 && a->ldw >= a->K, "stllm_gemv_w8: Wq null / not 16-byte aligned, or bad ldw %lld", (long long)a->ldw);
+  STLLM_CHECK_ARG(a->scale != nullptr, "stllm_gemv_w8: scale is null");
+  if (a->a_norm_x) {
+    STLLM_CHECK_ARG(a->a_norm_gamma && aligned16(a->a_norm_x) && aligned16(a->a_norm_gamma) && a->a_norm_ldx >= a->K && a->a_norm_ldx % 4 == 0 && a->a_rows_per_batch == 0,
+                    "stllm_gemv_w8(a_norm): the fused RMSNorm operand needs flat 16-byte aligned fp32 rows and gamma (M=%d)", a->M);
+  } else {
+    STLLM_CHECK_ARG(a->A && aligned16(a->A) && (a->lda * 2) % 16 == 0 && a->lda >= a->K && (a->a_batch_stride * 2) % 16 == 0,
+                    "stllm_gemv_w8: A null / not 16-byte aligned, or bad lda %lld", (long long)a->lda);
+  }
+  STLLM_CHECK_ARG(a->out != nullptr && aligned16(a->out), "stllm_gemv_w8: out null or not 16-byte aligned");
+  if (a->epilogue < STLLM_EPI_STORE || a->epilogue > STLLM_EPI_ROPE) {
+    stllm_set_error("stllm_gemv_w8: epilogue %d is not one of STORE / RESID / SWIGLU / ROPE", a->epilogue);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  {
+    const bool f32o = a->epilogue == STLLM_EPI_RESID || (a->epilogue == STLLM_EPI_STORE && a->out_is_f32);
+    const int oes = f32o ? 4 : 2;
+    STLLM_CHECK_ARG((a->ldo * oes) % 16 == 0 && (a->o_batch_stride * oes) % 16 == 0,
+                    "stllm_gemv_w8: output row/batch stride must be a multiple of 16 bytes (ldo=%lld)", (long long)a->ldo);
+  }
+  if (a->epilogue == STLLM_EPI_RESID)
+    STLLM_CHECK_ARG(a->resid != nullptr && aligned16(a->resid) && a->ldr % 4 == 0, "stllm_gemv_w8(RESID): resid null / misaligned");
+  if (a->epilogue == STLLM_EPI_ROPE)
+    STLLM_CHECK_ARG(a->rope_cos && a->rope_sin && a->rope_seq > 0 && a->rope_cols % 128 == 0, "stllm_gemv_w8(ROPE): need cos/sin tables, rope_seq, rope_cols%%128==0");
+  if (a->M > 16) {
+    stllm_set_error("stllm_gemv_w8: M=%d is outside the decode regime (M <= 16)", a->M);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  if (a->a_norm_x && a->M > 2) {
+    stllm_set_error("stllm_gemv_w8(a_norm): no kernel for M=%d with the fused RMSNorm operand (M <= 2): run stllm_rmsnorm first", a->M);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  const int g_gemv_mfma = stllm_options().gemv_mfma;
+  const int from = g_gemv_mfma == 0 ? 17 : g_gemv_mfma >= 1 ? g_gemv_mfma : 3;   // n >= 1: from M = n
+  const bool mfma = !a->a_norm_x && a->M >= from && a->K % 64 == 0;
+  if (!mfma) {   // the VALU kernel: its staged rows must fit the LDS
+    const int mr = a->M <= 2 ? a->M : (a->M + 1) / 2 * 2;
+    if (a->M > 8 || (int64_t)mr * a->K * 2 > 150 * 1024) {
+      stllm_set_error("stllm_gemv_w8: no kernel for M=%d K=%d%s (matrix-core kernel: K %% 64 == 0, no a_norm, option gemv_mfma=%d; VALU kernel: M <= 8 and %d x K x 2 bytes <= 150 KiB)",
+                      a->M, a->K, a->a_norm_x ? " with a_norm" : "", g_gemv_mfma, mr);
+      return STLLM_ERR_UNSUPPORTED;
+    }
+  }
+  sg::GemmParams p{};
+  p.A = reinterpret_cast<const char*>(a->A); p.lda_b = a->lda * 2;
+  p.W = reinterpret_cast<const char*>(a->Wq); p.ldw_b = a->ldw;
+  p.bias = a->bias; p.out = a->out; p.ldo = a->ldo; p.resid = a->resid; p.ldr = a->ldr;
+  p.aux0 = a->rope_cos; p.aux1 = a->rope_sin; p.rope_seq = a->rope_seq; p.rope_cols = a->rope_cols;
+  p.M = a->M; p.N = a->N; p.K = a->K; p.act = STLLM_ACT_NONE; p.out_is_f32 = a->out_is_f32;
+  p.nx = a->a_norm_x; p.nx_ld = a->a_norm_ldx; p.ngamma = a->a_norm_gamma; p.neps = a->a_norm_eps;
+  p.a_rpb = a->a_rows_per_batch; p.a_bs_b = a->a_batch_stride * 2;
+  p.o_rpb = a->o_rows_per_batch; p.o_bs = a->o_batch_stride;
+  stllm_gemm_args key{};   // what stllm_gemm_profile keys and reports a launch by; dtype + 16 keeps the int8 launches apart from 16-bit ones of the same shape
+  key.dtype = a->dtype + 16; key.epilogue = a->epilogue; key.out_is_f32 = a->out_is_f32; key.M = a->M; key.N = a->N; key.K = a->K;
+  const int prof_rec = stllm_prof_begin(&key, stream_);
+  const int rc = a->dtype == STLLM_BF16 ? dispatch_gemv_w8<bf16_t>(a->epilogue, p, a->scale, mfma, stream)
+                                        : dispatch_gemv_w8<f16_t>(a->epilogue, p, a->scale, mfma, stream);
+  stllm_prof_end(prof_rec, rc, &key, stream_);
+  return rc;
 }

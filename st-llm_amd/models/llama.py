@@ -15,6 +15,11 @@ buffer of every layer IS the cache — ``KVCache`` owns one [B, max_len, 3*D] bu
 [0, S) of it through the 2-level row indexing, a decode step writes row `len` (RoPE at that position) and attends over
 rows [0, len] in place: no copies, no re-layout.  Decode reuses the prefill kernels (small-M tiles); GEMV-regime kernels
 are future work.
+
+Int8 decode weights (runtime.set_decode_weights("int8")): decode_step streams an int8 copy of the four packed projection weights of every
+layer (pack.quant8_rows: one fp32 scale per output row) through the W8A16 kernels (hip.gemv_w8) — half the bytes per token.  The copy lives
+NEXT TO the 16-bit weights, which prefill / extend keep using: + 6.6 GB at 7B on top of the 13.5 GB of the 16-bit pack.  This is the
+reference's `device_8bit` knob (demo.py:41) with something behind it.
 """
 import os
 
@@ -139,6 +144,7 @@ class LlamaModel(nn.Module):
         self.layers = nn.ModuleList([LlamaDecoderLayer(config, device) for _ in range(config.num_hidden_layers)])
         self.norm = RMSNorm(config.hidden_size, config.rms_norm_eps, device)
         self._packed = {}
+        self._packed_w8 = {}   # dt -> (fingerprint, per-layer {wqkv, wo, wgu, wdown: (q int8, scale f32)}): the int8 decode weights, built on first use
         self._rope = {}
         self._carr = {}   # C-side table of the packed layers (+ the cache it points into): rebuilt when either changes
         self._plist = ParamList(lambda: self.layers.parameters())
@@ -158,6 +164,22 @@ class LlamaModel(nn.Module):
             lora = self.lora_active() and lora_mod.any_nonzero_b(self)   # (one device read per pack miss)
             hit = (fp, [l.pack(dt, self.config.num_attention_heads, frag=self.wd_frag, lora=lora) for l in self.layers])
             self._packed[dt] = hit
+        return hit[1]
+
+    def pack_w8(self, dtype=None):
+        """the int8 decode weights: per layer {wqkv, wo, wgu, wdown} -> (q int8 [N, K], scale f32 [N]), quantised from the packed 16-bit weights
+        of pack(dt) (so the RoPE / gate-up row orders are inherited) and cached under the same parameter fingerprint (layers.params_fingerprint:
+        `_version` + `data_ptr()`): rebuilt, like the 16-bit pack, after an in-place edit of a master (p.copy_, p.mul_, an optimizer step through
+        torch), load_state_dict or .to(device); a write through `p.data` or through a raw pointer bumps no version counter — such writers call
+        repack(), which drops both.  Also dropped when runtime.set_decode_weights(None) is seen by the next decode_step.  + 6.6 GB at 7B."""
+        dt = hip.torch_dtype(dtype) if dtype is not None else runtime.compute_dtype()
+        layers = self.pack(dt)
+        fp = self._packed[dt][0]
+        hit = self._packed_w8.get(dt)
+        if hit is None or hit[0] != fp:
+            self._packed_w8 = {}   # one copy at a time
+            hit = (fp, [{k: pack.quant8_rows(pk[k]) for k in ("wqkv", "wo", "wgu", "wdown")} for pk in layers])
+            self._packed_w8[dt] = hit
         return hit[1]
 
     def add_lora(self, r, lora_alpha=32):
@@ -181,11 +203,13 @@ class LlamaModel(nn.Module):
 
     def repack(self):
         self._packed = {}
+        self._packed_w8 = {}
         self._carr = {}
         self._plist.reset()
 
     def _load_from_state_dict(self, *a, **k):
         self._packed = {}
+        self._packed_w8 = {}
         self._carr = {}
         self._plist.reset()
         return super()._load_from_state_dict(*a, **k)
@@ -425,8 +449,18 @@ class LlamaModel(nn.Module):
         cache and returns (hidden f32 [B,1,D] after model.norm, hidden compute-dtype [B,D])."""
         cfg = self.config
         dt = runtime.compute_dtype()
+        if runtime.decode_weights() == "int8" and dt == torch.float32:
+            raise NotImplementedError(f"int8 decode weights need a 16-bit compute mode (bf16 / fp16), not {runtime.mode_name()!r}")
         layers = self.pack(dt)
         B, _, D = x_new.shape
+        w8 = None
+        if runtime.decode_weights() == "int8":
+            if "lora_A" in layers[0]:
+                raise NotImplementedError("int8 decode weights with active LoRA adapters: merge_adapter() first")
+            if B <= 16:   # the decode regime of hip.gemv_w8; larger batches stream the 16-bit weights on the tile kernels
+                w8 = self.pack_w8(dt)
+        elif self._packed_w8:
+            self._packed_w8 = {}   # the mode was switched off: free the int8 copy
         H = cfg.num_attention_heads
         hd = D // H
         pos = cache.len
@@ -441,6 +475,9 @@ class LlamaModel(nn.Module):
         fuse = dt != torch.float32 and B <= FUSE_NORM_ROWS
         for li_, pk in enumerate(layers):
             row = cache.qkv[li_][:, pos]                                   # [B, 3D] view, row stride max_len*3D
+            if w8 is not None:   # the same step over the int8 weights (W8A16 kernels): same epilogues, same fused norms
+                self.decode_layer_w8(x, pk, w8[li_], row, cache, li_, pos, cpos, spos, fuse and B <= 2, dt)   # (stllm_gemv_w8 fuses the norm for <= 2 rows)
+                continue
             if "lora_A" in pk:   # active adapters: the fused-RMSNorm GEMV cannot see t = h A^T — norm, down projection, then the GEMV over K = D + P
                 hip.gemm(self.qkv_operand(x, pk, dt), pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=1, rope_cols=2 * D, out=row)
             elif fuse:
@@ -463,6 +500,31 @@ class LlamaModel(nn.Module):
         cache.len = pos + 1
         h16, h32 = hip.rmsnorm(x, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
         return h32.view(B, 1, D), h16
+
+    def decode_layer_w8(self, x, pk, q8, row, cache, li_, pos, cpos, spos, fuse, dt):
+        """one decoder layer of decode_step with its four projections on hip.gemv_w8 (q8: pack_w8's entry of the layer); attention and norms as in the 16-bit step"""
+        cfg = self.config
+        B, D = x.shape
+        H = cfg.num_attention_heads
+        hd = D // H
+        ML3 = cache.max_len * 3 * D
+        if fuse:
+            hip.gemv_w8(None, *q8["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=1, rope_cols=2 * D, out=row,
+                        a_norm=(x, pk["ln1"], cfg.rms_norm_eps))
+        else:
+            h, _ = hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)
+            hip.gemv_w8(h, *q8["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=1, rope_cols=2 * D, out=row)
+        full = cache.qkv[li_].view(B * cache.max_len, 3 * D)
+        a = hip.attention(row[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=1, Skv=pos + 1, D=hd,
+                          scale=hd ** -0.5, causal=False, q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D),
+                          v_strides=(ML3, 3 * D))
+        hip.gemv_w8(a, *q8["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
+        if fuse:
+            g = hip.gemv_w8(None, *q8["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, a_norm=(x, pk["ln2"], cfg.rms_norm_eps))
+        else:
+            h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
+            g = hip.gemv_w8(h, *q8["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU)
+        hip.gemv_w8(g, *q8["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
 
     def new_cache(self, batch, max_len, device):
         return KVCache(len(self.layers), batch, max_len, self.config.hidden_size, runtime.compute_dtype(), device)

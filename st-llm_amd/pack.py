@@ -14,6 +14,8 @@ parameter lives on); none changes the mathematical function:
 * ``llama_gate_up``  — gate/up_proj interleaved in groups of 32 rows ([32 gate | 32 up] per 64-column
                        wave tile) for the fused SiLU(gate)*up epilogue (modeling_llama_mem.py:143-144).
 * ``bert_qkv`` / ``bert_kv`` — Q-Former query/key/value fused (Qformer.py:127-133).
+* ``quant8_rows``    — the one packer that is NOT exact: a packed 16-bit weight -> int8 rows + one fp32 scale per row, the
+                       weight format of the W8A16 decode kernels (hip.gemv_w8).
 """
 import os
 
@@ -82,6 +84,22 @@ def llama_gate_up(wg, wu, dtype):
     u = _cast(wu, dtype)
     k = g.shape[1]   # 3 K in the split mode
     return torch.stack((g.view(n // 32, 32, k), u.view(n // 32, 32, k)), dim=1).reshape(2 * n, k).contiguous()
+
+
+def quant8_rows(w16):
+    """packed weight [N, K] -> (q int8 [N, K] contiguous, scale f32 [N]) for hip.gemv_w8: symmetric, one scale per output row.
+    amax = max |w| over the row (fp32); scale = amax / 127, an fp32 division (1 for an all-zero row); q = clamp(rint(w / scale), -127, 127),
+    round-half-even (-128 never occurs).  The quotient w / scale is taken in fp64, where w and scale are exact: an fp32 quotient can be rounded
+    ONTO a tie k + 1/2 from below and then away from w (measured: |w - q scale| = (1 + 3.5e-6) scale / 2), the fp64 one keeps
+    |w - q scale| <= scale / 2 (1 + 2^-20).  Every step is one correctly rounded IEEE operation, so the CPU and the device agree bit for bit.
+    Works on the PACKED weight: the RoPE head permutation of llama_qkv and
+    the [32 gate | 32 up] interleave of llama_gate_up are row permutations, and a per-row scale commutes with those."""
+    assert w16.dim() == 2
+    wf = w16.detach().float()
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / 127.0, torch.ones_like(amax))
+    q = torch.clamp(torch.round(wf.double() / scale.double()[:, None]), -127.0, 127.0).to(torch.int8)
+    return q.contiguous(), scale.contiguous()
 
 
 def frag32(w):

@@ -12,14 +12,21 @@
              shows the ViT is the stage whose fp16 error stays under the bar (9.5e-3 alone; the Q-Former's is 1.3e-2, Llama's 2.3e-2), and it is
              45 % of the GEMM time — the step costs 1.8x the bf16 step instead of 2.8x.  Measured at full size: c2 9.4e-3, c3 9.8e-3, c4 1.02e-2 — AT the 1e-2 bar, not
              safely under it: "bf16x3" stays the verify mode.  The visual encoder enters `vit_scope()` for its forward (the BT-Adapter backbone does not: it stays bf16x3).
+
+Next to the numerics mode, the DECODE WEIGHT format (set_decode_weights): None — the one-token step streams the 16-bit weights the prefill uses
+(default) — or "int8": LlamaModel.decode_step runs its four projections per layer on the W8A16 kernels (hip.gemv_w8) over an int8 copy of the
+packed weights with one fp32 scale per output row.  Prefill, training, lm_head and attention are not affected.  STLLM_DECODE_WEIGHTS=int8 in the
+environment makes it the default of a process (the tools).
 """
 import contextlib
+import os
 
 import torch
 
 from .hip import torch_dtype
 
 _state = {"dtype": torch.bfloat16, "split": False, "vit": None}
+_decode = {"weights": None}
 SPLIT_NAMES = ("bf16x3", "split")
 MIXED_VIT = "fp16"   # the ViT's mode inside "mixed"
 
@@ -71,3 +78,28 @@ def use_dtype(d):
         yield
     finally:
         _state.update(old)
+
+
+def set_decode_weights(w):
+    """None | "int8" (see the module docstring)"""
+    if w not in (None, "int8"):
+        raise ValueError(f"decode weights: None or 'int8', got {w!r}")
+    _decode["weights"] = w
+
+
+def decode_weights():
+    return _decode["weights"]
+
+
+@contextlib.contextmanager
+def use_decode_weights(w):
+    old = _decode["weights"]
+    set_decode_weights(w)
+    try:
+        yield
+    finally:
+        _decode["weights"] = old
+
+
+if os.environ.get("STLLM_DECODE_WEIGHTS"):
+    set_decode_weights(os.environ["STLLM_DECODE_WEIGHTS"])
