@@ -361,6 +361,31 @@ int stllm_attention_decode(int dtype, const void* q, int64_t q_bs, const void* k
                            int D, float scale, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
+ * Ragged decode attention (additive to ABI 7): stllm_attention_decode for a KV cache whose batch rows have DIFFERENT lengths.
+ * kv_len: int32 [B] in device memory; row b attends keys [0, min(kv_len[b], max_kv)); max_kv is the host-known upper bound of the lengths, from which the
+ * schedule (single pass | split-KV pair, "attn_decode_single") and the grid are chosen exactly as stllm_attention_decode chooses them from Skv.  A row with
+ * kv_len[b] <= 0 (a free slot of the batch) gets zeros, never NaN.  Row b's output is bit-identical to stllm_attention_decode on that row alone with
+ * Skv = kv_len[b] whenever that call takes the same schedule: same key-to-lane assignment, and in the split pair the split count and keys per split of its
+ * own length, merged in the same order.  bf16 / fp16 at head_dim 128 only: anything else returns STLLM_ERR_UNSUPPORTED (fp32: stllm_attention with kv_len).
+ * Addressing as for stllm_attention_decode; workspace: >= stllm_attention_decode_ragged_workspace_bytes(B, H, max_kv) bytes, 16-byte aligned.
+ */
+int64_t stllm_attention_decode_ragged_workspace_bytes(int B, int H, int max_kv);
+int stllm_attention_decode_ragged(int dtype, const void* q, int64_t q_bs, const void* k, int64_t k_bs, int64_t k_rs,
+                                  const void* v, int64_t v_bs, int64_t v_rs, void* out, int64_t o_bs, int B, int H,
+                                  const int32_t* kv_len, int max_kv, int D, float scale, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+
+/*
+ * Ragged KV-cache append (additive to ABI 7): for every batch row b the [k | v] columns (with_q != 0: [q | k | v]) of the dense fused row
+ * src[b*ld_src .. + 3*hidden) are copied to cache[b*batch_stride + pos[b]*row_stride + the same columns].  pos: int32 [B] in device memory; a position
+ * outside [0, max_len) marks a free slot: nothing is written for that row.  All strides in elements of `dtype` (bf16 / fp16 / fp32).  16-byte vector
+ * copies: pointers, hidden * esize and every stride * esize must be multiples of 16 bytes.  The QKV GEMV writes rows at ONE stride only, so a ragged
+ * decode step lets it write a dense [B, 3*hidden] scratch and scatters from there.
+ */
+int stllm_kv_append_rows(int dtype, const void* src, int64_t ld_src, void* cache, int64_t batch_stride, int64_t row_stride,
+                         const int32_t* pos, int B, int hidden, int max_len, int with_q, void* stream);
+
+/*
  * Frame preprocessing in front of the path — replaces the CPU transform chain of Chat.__init__ / upload_video
  * (stllm/conversation/conversation.py:190-198, 276-279; stllm/test/video_transforms.py:54-60, 94-124, 367-407):
  *   GroupScale(224, BICUBIC) -> GroupCenterCrop(224) -> Stack -> ToTorchFormatTensor -> GroupNormalize(CLIP mean / std)

@@ -117,3 +117,42 @@ class Chat:
         if tok.numel() and int(tok[0]) == 1:
             tok = tok[1:]
         return self.model.llama_tokenizer.decode(tok.tolist()), tok.cpu().numpy()
+
+    def answer_many(self, img_list, questions_ids, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9,
+                    repetition_penalty=1.0, length_penalty=1, temperature=1.0, max_length=2000, do_sample=False,
+                    stop_sequences=None, instruction=False, prefix=None, **kw):
+        """N questions about ONE video in one ragged batch (generate(batching="ragged")): answer()'s truncation rule and its repetition_penalty = 1.5
+        override per question, Chat's stop tokens as per-row stop_sequences (a row that ends in '###' is finished, the others go on).  prefix: a
+        prefill_video(img_list) result — the video is prefilled once, forked to the N rows, and only [BOS] + question runs per row.  Returns one
+        (text, ids) pair per question, each what answer() returns for that question alone."""
+        pairs = [self.get_context_emb_ids(img_list, q) for q in questions_ids]
+        if not instruction:
+            repetition_penalty = 1.5
+        keep = max_length - max_new_tokens
+        embs = [e[0, max(0, e.shape[1] - keep):] for e, _ in pairs]
+        if prefix is not None and all(e.shape[1] <= keep for e, _ in pairs):   # (a truncated prompt would cut into the cached positions: whole prompts below)
+            assert prefix.n_tokens == img_list[0].shape[1] == prefix.cache.len
+            embs = [e[prefix.n_tokens:] for e in embs]
+            kw = dict(kw, prefix_cache=prefix.cache)
+        lens = [e.shape[0] for e in embs]
+        batch = torch.zeros((len(embs), max(lens), embs[0].shape[-1]), dtype=embs[0].dtype, device=embs[0].device)
+        mask = torch.zeros((len(embs), max(lens)), dtype=torch.long)
+        for b, e in enumerate(embs):
+            batch[b, :lens[b]] = e
+            mask[b, :lens[b]] = 1
+        if stop_sequences is None:
+            stop_sequences = self.stopping_criteria[0].stops
+        out, n_out = self.LLM.generate(inputs_embeds=batch, attention_mask=mask, max_new_tokens=max_new_tokens, stop_sequences=stop_sequences,
+                                       num_beams=num_beams, do_sample=do_sample, min_length=min_length, top_p=top_p, batching="ragged",
+                                       repetition_penalty=repetition_penalty, length_penalty=length_penalty, temperature=temperature,
+                                       return_lengths=True, **kw)
+        hip.gemm_workspace_check(batch.device, wait=True) if batch.is_cuda else None
+        res = []
+        for row, n in zip(out, n_out):
+            tok = row[:n]
+            if tok.numel() and int(tok[0]) == 0:   # conversation.py:246-249
+                tok = tok[1:]
+            if tok.numel() and int(tok[0]) == 1:
+                tok = tok[1:]
+            res.append((self.model.llama_tokenizer.decode(tok.tolist()), tok.cpu().numpy()))
+        return res

@@ -1328,6 +1328,54 @@ template <> __device__ __forceinline__ void widen2<f16_t>(uint32_t u, float& a, 
   b = (float)__builtin_bit_cast(_Float16, (uint16_t)(u >> 16));
 }
 
+// the body of one split-KV workgroup of the RAGGED kernel: keys [k0, k1) of (b, h), partial state -> its record (Skv, split count and keys per split are
+// read per batch row by the caller).  The same key-to-lane assignment and merge order as attn_decode_partial_kernel below, so equal lengths give equal bits.
+template <typename T>
+__device__ __forceinline__ void decode_partial_body(const AttnParams& p, float (&part)[4][kDecRec], float* __restrict__ ws, int rec_stride, int sp, int b, int h, int k0, int k1) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float q0, q1;
+  widen2<T>(*reinterpret_cast<const uint32_t*>(p.q + ((int64_t)b * p.q_bs + (int64_t)h * kDecD + 2 * lane) * 2), q0, q1);
+  q0 *= p.scale_log2;
+  q1 *= p.scale_log2;
+  const char* kb = p.k + ((int64_t)b * p.k_bs + (int64_t)h * kDecD + 2 * lane) * 2;
+  const char* vb = p.v + ((int64_t)b * p.v_bs + (int64_t)h * kDecD + 2 * lane) * 2;
+  float m = kNeg, l = 0.0f, o0 = 0.0f, o1 = 0.0f;
+  for (int key = k0 + wave; key < k1; key += 4) {
+    float ka, kc, va, vc;
+    widen2<T>(*reinterpret_cast<const uint32_t*>(kb + (int64_t)key * p.k_rs * 2), ka, kc);
+    widen2<T>(*reinterpret_cast<const uint32_t*>(vb + (int64_t)key * p.v_rs * 2), va, vc);
+    const float s = wave_sum(fmaf(q0, ka, q1 * kc));   // log2-domain score, identical in every lane
+    const float mn = fmaxf(m, s);
+    const float alpha = __builtin_amdgcn_exp2f(m - mn), pr = __builtin_amdgcn_exp2f(s - mn);
+    l = fmaf(l, alpha, pr);
+    o0 = fmaf(o0, alpha, pr * va);
+    o1 = fmaf(o1, alpha, pr * vc);
+    m = mn;
+  }
+  if (lane == 0) { part[wave][0] = m; part[wave][1] = l; }
+  part[wave][2 + 2 * lane] = o0;
+  part[wave][3 + 2 * lane] = o1;
+  __syncthreads();
+  if (wave == 0) {
+    float mm = fmaxf(fmaxf(part[0][0], part[1][0]), fmaxf(part[2][0], part[3][0]));
+    float ll = 0.0f, a0 = 0.0f, a1 = 0.0f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float f = __builtin_amdgcn_exp2f(part[w][0] - mm);
+      ll = fmaf(part[w][1], f, ll);
+      a0 = fmaf(part[w][2 + 2 * lane], f, a0);
+      a1 = fmaf(part[w][3 + 2 * lane], f, a1);
+    }
+    float* rec = ws + (((int64_t)b * p.H + h) * rec_stride + sp) * kDecRec;   // rec_stride: records per (batch, head) = the split count of the grid
+    if (lane == 0) { rec[0] = mm; rec[1] = ll; }
+    rec[2 + 2 * lane] = a0;
+    rec[3 + 2 * lane] = a1;
+  }
+}
+
+// The uniform split-KV workgroup keeps its own copy of the loop above, statement for statement: routed through decode_partial_body the compiler schedules it
+// differently (profiles/ragged_decode_uniform_isa_diff.log), and the uniform path's instruction streams are not to change with the ragged feature.  The two
+// copies must stay in step: tests/test_ragged_gpu.py::test_attention_decode_ragged compares them bit for bit.
 template <typename T>
 __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const AttnParams p, float* __restrict__ ws, int nsplit, int keys_per_split) {
   __shared__ float part[4][kDecRec];
@@ -1375,9 +1423,9 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(const AttnPara
 }
 
 template <typename T>
-__global__ __launch_bounds__(64) void attn_decode_merge_kernel(const AttnParams p, const float* __restrict__ ws, int nsplit) {
-  const int lane = threadIdx.x, h = blockIdx.x, b = blockIdx.y;
-  const float* rec = ws + ((int64_t)b * p.H + h) * nsplit * kDecRec;
+__device__ __forceinline__ void decode_merge_body(const AttnParams& p, const float* __restrict__ ws, int rec_stride, int nsplit, int b, int h) {
+  const int lane = threadIdx.x;
+  const float* rec = ws + ((int64_t)b * p.H + h) * rec_stride * kDecRec;
   float mm = kNeg;
   for (int s = 0; s < nsplit; ++s) mm = fmaxf(mm, rec[s * kDecRec]);
   float ll = 0.0f, a0 = 0.0f, a1 = 0.0f;
@@ -1390,6 +1438,12 @@ __global__ __launch_bounds__(64) void attn_decode_merge_kernel(const AttnParams 
   const float inv = 1.0f / ll;
   uint32_t* op = reinterpret_cast<uint32_t*>(p.o + ((int64_t)b * p.o_bs + (int64_t)h * kDecD + 2 * lane) * 2);
   *op = Elem<T>::pack2(a0 * inv, a1 * inv);
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void attn_decode_merge_kernel(const AttnParams p, const float* __restrict__ ws, int nsplit) {
+  const int h = blockIdx.x, b = blockIdx.y;
+  decode_merge_body<T>(p, ws, nsplit, nsplit, b, h);
 }
 
 // ---- single-pass decode attention (round 2): ONE workgroup of 16 waves per (batch, head) ---------------------------------------
@@ -1418,12 +1472,11 @@ template <> __device__ __forceinline__ void widen8v<f16_t>(i32x4 v, float* f) {
   }
 }
 
+// body shared by the uniform kernel (Skv = p.Skv) and the ragged one (Skv = the batch row's own length, workgroup-uniform)
 template <typename T>
-__global__ __launch_bounds__(64 * kDecWaves) void attn_decode_single_kernel(const AttnParams p) {
-  __shared__ float part[kDecWaves * 4][kDecRec];   // one (m, l, O[128]) record per 16-lane group
+__device__ __forceinline__ void decode_single_body(const AttnParams& p, float (&part)[kDecWaves * 4][kDecRec], int b, int h, int Skv) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int grp = lane >> 4, l16 = lane & 15;     // key within the wave's quad, dims 8 * l16 .. + 7
-  const int h = blockIdx.x, b = blockIdx.y;
   float q[8];
   widen8v<T>(*reinterpret_cast<const i32x4*>(p.q + ((int64_t)b * p.q_bs + (int64_t)h * kDecD + 8 * l16) * 2), q);
 #pragma unroll
@@ -1436,16 +1489,16 @@ __global__ __launch_bounds__(64 * kDecWaves) void attn_decode_single_kernel(cons
   const int step = kDecWaves * 4;
   int kbase = wave * 4;                              // wave-uniform: all four lane groups run the same number of steps
   i32x4 kn = {0, 0, 0, 0}, vn = {0, 0, 0, 0};
-  if (kbase + grp < p.Skv) {
+  if (kbase + grp < Skv) {
     kn = *reinterpret_cast<const i32x4*>(kb + (int64_t)(kbase + grp) * p.k_rs * 2);
     vn = *reinterpret_cast<const i32x4*>(vb + (int64_t)(kbase + grp) * p.v_rs * 2);
   }
-  for (; kbase < p.Skv; kbase += step) {
+  for (; kbase < Skv; kbase += step) {
     const int key = kbase + grp;
-    const bool live = key < p.Skv;
+    const bool live = key < Skv;
     const i32x4 kc = kn, vc = vn;
     const int nk = key + step;
-    if (nk < p.Skv) {   // request the next quad of this wave before this one is consumed
+    if (nk < Skv) {   // request the next quad of this wave before this one is consumed
       kn = *reinterpret_cast<const i32x4*>(kb + (int64_t)nk * p.k_rs * 2);
       vn = *reinterpret_cast<const i32x4*>(vb + (int64_t)nk * p.v_rs * 2);
     }
@@ -1487,10 +1540,53 @@ __global__ __launch_bounds__(64 * kDecWaves) void attn_decode_single_kernel(cons
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(64 * kDecWaves) void attn_decode_single_kernel(const AttnParams p) {
+  __shared__ float part[kDecWaves * 4][kDecRec];   // one (m, l, O[128]) record per 16-lane group
+  decode_single_body<T>(p, part, blockIdx.y, blockIdx.x, p.Skv);
+}
+
 // stllm_set_option("attn_decode_single", 0): always the split-KV pair (tests compare both)
-static int decode_splits(int Skv) {
+__host__ __device__ static inline int decode_splits(int Skv) {
   int n = (Skv + 47) / 48;   // ~48 keys (12 per wave) per workgroup
   return n < 1 ? 1 : (n > 64 ? 64 : n);
+}
+
+// ---- ragged decode attention: every batch row has its own number of cached keys (kv_len[b], device memory; max_kv bounds it on the host) -------
+// The bodies above with the length read once per workgroup.  Row b of the split pair uses the split count and keys per split that the uniform call
+// gives Skv = kv_len[b] (decode_splits): the grid is sized for max_kv, surplus workgroups exit, the merge reads the records its row wrote — at the
+// record stride of the grid (nsplit_max).  A row of length 0 (a free slot of the batch) writes zeros.
+__device__ __forceinline__ void decode_zero_row(const AttnParams& p, int b, int h) {
+  if (threadIdx.x < 64) *reinterpret_cast<uint32_t*>(p.o + ((int64_t)b * p.o_bs + (int64_t)h * kDecD + 2 * threadIdx.x) * 2) = 0u;
+}
+
+template <typename T>
+__global__ __launch_bounds__(64 * kDecWaves) void attn_decode_single_ragged_kernel(const AttnParams p) {
+  __shared__ float part[kDecWaves * 4][kDecRec];
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int len = min(p.kv_len[b], p.Skv);
+  if (len <= 0) { decode_zero_row(p, b, h); return; }
+  decode_single_body<T>(p, part, b, h, len);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_decode_partial_ragged_kernel(const AttnParams p, float* __restrict__ ws, int nsplit_max) {
+  __shared__ float part[4][kDecRec];
+  const int sp = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int len = min(p.kv_len[b], p.Skv);
+  const int nsplit = decode_splits(len);
+  if (len <= 0 || sp >= nsplit) return;
+  const int kps = (len + nsplit - 1) / nsplit;
+  const int k0 = sp * kps, k1 = min(len, k0 + kps);
+  decode_partial_body<T>(p, part, ws, nsplit_max, sp, b, h, k0, k1);
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void attn_decode_merge_ragged_kernel(const AttnParams p, const float* __restrict__ ws, int nsplit_max) {
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int len = min(p.kv_len[b], p.Skv);
+  if (len <= 0) { decode_zero_row(p, b, h); return; }
+  decode_merge_body<T>(p, ws, nsplit_max, decode_splits(len), b, h);
 }
 
 extern "C" int stllm_attention(int dtype, const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs,
@@ -1704,6 +1800,56 @@ extern "C" int stllm_attention_decode(int dtype, const void* q, int64_t q_bs, co
     hipLaunchKernelGGL(attn_decode_merge_kernel<f16_t>, dim3(H, B), dim3(64), 0, stream, p, ws, nsplit);
   }
   STLLM_CHECK_LAUNCH("stllm_attention_decode");
+  return STLLM_OK;
+}
+
+extern "C" int64_t stllm_attention_decode_ragged_workspace_bytes(int B, int H, int max_kv) {
+  return stllm_attention_decode_workspace_bytes(B, H, max_kv);
+}
+
+// stllm_attention_decode with per-row lengths: row b attends keys [0, min(kv_len[b], max_kv)).  The schedule (single pass | split-KV pair) and the grid come
+// from max_kv exactly as stllm_attention_decode derives them from Skv; the per-row bounds live in the kernels.
+extern "C" int stllm_attention_decode_ragged(int dtype, const void* q, int64_t q_bs, const void* k, int64_t k_bs, int64_t k_rs,
+                                             const void* v, int64_t v_bs, int64_t v_rs, void* out, int64_t o_bs, int B, int H,
+                                             const int32_t* kv_len, int max_kv, int D, float scale, void* workspace,
+                                             int64_t workspace_bytes, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  STLLM_CHECK_ARG(q && k && v && out && workspace && kv_len, "stllm_attention_decode_ragged: null pointer");
+  STLLM_CHECK_ARG(B > 0 && H > 0 && max_kv > 0, "stllm_attention_decode_ragged: empty problem");
+  if (D != kDecD || (dtype != STLLM_BF16 && dtype != STLLM_F16)) {
+    stllm_set_error("stllm_attention_decode_ragged: head_dim %d / dtype %d unsupported (bf16 / fp16 at head_dim 128; fp32: stllm_attention with kv_len)", D, dtype);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  STLLM_CHECK_ARG(((uintptr_t)q & 3) == 0 && ((uintptr_t)k & 3) == 0 && ((uintptr_t)v & 3) == 0 && ((uintptr_t)out & 3) == 0 &&
+                      ((uintptr_t)kv_len & 3) == 0 && q_bs % 2 == 0 && k_bs % 2 == 0 && k_rs % 2 == 0 && v_bs % 2 == 0 && v_rs % 2 == 0 && o_bs % 2 == 0,
+                  "stllm_attention_decode_ragged: pointers / strides must be 4-byte aligned");
+  const int nsplit = decode_splits(max_kv);
+  STLLM_CHECK_ARG(workspace_bytes >= stllm_attention_decode_ragged_workspace_bytes(B, H, max_kv) && aligned16(workspace),
+                  "stllm_attention_decode_ragged: workspace too small or misaligned");
+  AttnParams p{};
+  p.q = (const char*)q; p.q_bs = q_bs;
+  p.k = (const char*)k; p.k_bs = k_bs; p.k_rs = k_rs;
+  p.v = (const char*)v; p.v_bs = v_bs; p.v_rs = v_rs;
+  p.o = (char*)out; p.o_bs = o_bs;
+  p.B = B; p.H = H; p.Sq = 1; p.Skv = max_kv; p.D = D;
+  p.scale = scale; p.scale_log2 = scale * 1.44269504088896340736f;
+  p.kv_len = kv_len;
+  if ((max_kv <= kDecSingleMax || B * H >= 256) && aligned16(q) && aligned16(k) && aligned16(v) && q_bs % 8 == 0 && k_bs % 8 == 0 &&
+      k_rs % 8 == 0 && v_bs % 8 == 0 && v_rs % 8 == 0 && stllm_options().attn_decode_single) {
+    if (dtype == STLLM_BF16) hipLaunchKernelGGL(attn_decode_single_ragged_kernel<bf16_t>, dim3(H, B), dim3(64 * kDecWaves), 0, stream, p);
+    else hipLaunchKernelGGL(attn_decode_single_ragged_kernel<f16_t>, dim3(H, B), dim3(64 * kDecWaves), 0, stream, p);
+    STLLM_CHECK_LAUNCH("stllm_attention_decode_ragged(single)");
+    return STLLM_OK;
+  }
+  float* ws = reinterpret_cast<float*>(workspace);
+  if (dtype == STLLM_BF16) {
+    hipLaunchKernelGGL(attn_decode_partial_ragged_kernel<bf16_t>, dim3(nsplit, H, B), dim3(256), 0, stream, p, ws, nsplit);
+    hipLaunchKernelGGL(attn_decode_merge_ragged_kernel<bf16_t>, dim3(H, B), dim3(64), 0, stream, p, ws, nsplit);
+  } else {
+    hipLaunchKernelGGL(attn_decode_partial_ragged_kernel<f16_t>, dim3(nsplit, H, B), dim3(256), 0, stream, p, ws, nsplit);
+    hipLaunchKernelGGL(attn_decode_merge_ragged_kernel<f16_t>, dim3(H, B), dim3(64), 0, stream, p, ws, nsplit);
+  }
+  STLLM_CHECK_LAUNCH("stllm_attention_decode_ragged");
   return STLLM_OK;
 }
 

@@ -113,7 +113,41 @@ __global__ __launch_bounds__(256) void cast_rows_kernel(const float* __restrict_
   }
 }
 
+// ragged KV-cache append: the [k | v] (or [q | k | v]) bytes of dense row b -> the cache row of batch entry b at position pos[b]; 16 bytes per lane.
+// A position outside [0, max_len) marks a free slot of the batch: nothing is written for it.
+__global__ __launch_bounds__(256) void kv_append_rows_kernel(const char* __restrict__ src, int64_t src_stride, char* __restrict__ cache,
+                                                             int64_t batch_stride, int64_t row_stride, const int32_t* __restrict__ pos,
+                                                             int max_len, int col0_bytes, int n16) {
+  const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+  const int ps = pos[b];
+  if (c >= n16 || ps < 0 || ps >= max_len) return;
+  const uint4 v = reinterpret_cast<const uint4*>(src + (int64_t)b * src_stride + col0_bytes)[c];
+  reinterpret_cast<uint4*>(cache + (int64_t)b * batch_stride + (int64_t)ps * row_stride + col0_bytes)[c] = v;
+}
+
 }  // namespace
+
+extern "C" int stllm_kv_append_rows(int dtype, const void* src, int64_t ld_src, void* cache, int64_t batch_stride, int64_t row_stride,
+                                    const int32_t* pos, int B, int hidden, int max_len, int with_q, void* stream) {
+  STLLM_CHECK_ARG(src && cache && pos, "stllm_kv_append_rows: null pointer");
+  STLLM_CHECK_ARG(B > 0 && hidden > 0 && max_len > 0, "stllm_kv_append_rows: bad B=%d hidden=%d max_len=%d", B, hidden, max_len);
+  int e;
+  switch (dtype) {
+    case STLLM_BF16: case STLLM_F16: e = 2; break;
+    case STLLM_F32: e = 4; break;
+    default: stllm_set_error("stllm_kv_append_rows: bad dtype %d", dtype); return STLLM_ERR_BAD_DTYPE;
+  }
+  STLLM_CHECK_ARG(ld_src >= 3 * (int64_t)hidden && row_stride >= 3 * (int64_t)hidden && batch_stride >= (int64_t)max_len * row_stride,
+                  "stllm_kv_append_rows: rows of 3 * hidden elements, max_len rows per batch entry");
+  STLLM_CHECK_ARG(((int64_t)hidden * e) % 16 == 0 && (ld_src * e) % 16 == 0 && (row_stride * e) % 16 == 0 && (batch_stride * e) % 16 == 0 &&
+                      aligned16(src) && aligned16(cache) && (reinterpret_cast<uintptr_t>(pos) & 3) == 0,
+                  "stllm_kv_append_rows: 16-byte vector copies need 16-byte aligned pointers, strides and hidden");
+  const int col0 = with_q ? 0 : hidden * e, n16 = (3 * hidden * e - col0) / 16;
+  hipLaunchKernelGGL(kv_append_rows_kernel, dim3((n16 + 255) / 256, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const char*>(src), ld_src * e, reinterpret_cast<char*>(cache), batch_stride * e, row_stride * e, pos, max_len, col0, n16);
+  STLLM_CHECK_LAUNCH("stllm_kv_append_rows");
+  return STLLM_OK;
+}
 
 extern "C" int stllm_gather_rows(const float* src_a, int64_t ld_a, const float* src_b, int64_t ld_b,
                                  const int32_t* idx_a, const float* add, int64_t ld_add, const int32_t* idx_add,

@@ -185,8 +185,8 @@ static int llama_layers_impl(const stllm_llama_layers_args* a, const stllm_llama
   const int M = a->B * a->S, D = a->hidden, hd = D / a->n_heads, e = esize(a->dtype), eh = (int)hsize(a->dtype);
   const bool x3 = a->dtype == STLLM_BF16X3;
   const int64_t ldh = x3 ? 3 * (int64_t)D : D + P, ldg = x3 ? 3 * (int64_t)a->inter : a->inter;
-  if (a->cache_max_len != 0 && (a->cache_max_len < a->S || a->kv_len != nullptr)) {
-    stllm_set_error("stllm_llama_layers: the KV cache needs max_len >= S and equal-length sequences");
+  if (a->cache_max_len != 0 && (a->cache_max_len < a->S || (a->kv_len != nullptr && pos0 >= 0))) {   // (prefill: kv_len masks the pad keys of a ragged cache)
+    stllm_set_error("stllm_llama_layers: the KV cache needs max_len >= S (and, behind a prefix, no kv_len)");
     return STLLM_ERR_BAD_SHAPE;
   }
   if (pos0 >= 0 && (a->cache_max_len < (int64_t)pos0 + a->S || x3)) {

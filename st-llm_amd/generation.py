@@ -18,6 +18,11 @@ the argument subset above (one return sequence, no beam groups):
   * the KV cache is re-ordered by `beam_idx` after every step (`LlamaForCausalLM._reorder_cache`, spec
     modeling_llama_mem.py:747-752) — here one index_select per layer on the fused QKV cache rows that are in use.
 
+Ragged batches (`lengths=`: per-row prompt lengths of a right-padded `inputs_embeds`): ONE prefill fills a ragged KV cache (KVCache.lens), the first logits
+come from row lengths[b] - 1 of each prompt, beams inherit their prompt's length, and every step appends token b at its own position — each row generates
+exactly as its unpadded prompt would alone.  `stop_sequences` finishes rows one by one (the reference's StoppingCriteriaSub looks at row 0 only and stops
+the whole batch, which is wrong for more than one prompt).
+
 With `inputs_embeds` and no `input_ids` the sequences HF scores start empty, so every length below counts generated tokens
 only.  The prompt is prefilled ONCE and its cache rows are replicated to the beams (HF prefills num_beams identical copies).
 """
@@ -81,16 +86,48 @@ def _stop(stopping_criteria, ids, scores):
     return stopping_criteria is not None and any(bool(sc(ids, scores)) for sc in stopping_criteria)
 
 
+def _ends_in_stop(ids, stop_sequences):
+    """bool [rows]: the row's ids end in one of the stop sequences (1-D id tensors)"""
+    hit = torch.zeros(ids.shape[0], dtype=torch.bool, device=ids.device)
+    for seq in stop_sequences:
+        n = seq.numel()
+        if 0 < n <= ids.shape[1]:
+            hit |= (ids[:, -n:] == seq.to(ids.device).view(1, n)).all(dim=1)
+    return hit
+
+
 class _CacheStepper:
     """next-token logits from the model: prefill once, then one decode step per token; rows can be re-ordered (beams)."""
 
-    def __init__(self, lm_wrapper, inputs_embeds, rows, max_new_tokens, use_cache=True, prefix=None):
+    def __init__(self, lm_wrapper, inputs_embeds, rows, max_new_tokens, use_cache=True, prefix=None, lengths=None):
         self.m, self.lm = lm_wrapper, lm_wrapper.model
         self.use_cache = use_cache
         emb = inputs_embeds.float()
         B, S, _ = emb.shape
         self.rep = rows // B                      # beams per prompt
-        if prefix is not None:
+        if lengths is not None:
+            # ragged prompts: row b of the right-padded `inputs_embeds` holds lengths[b] tokens.  One prefill (or one extend behind the prefix) fills a ragged
+            # cache; the first logits are those of each prompt's LAST real token; the beams of a prompt are copies of its row and inherit its length.
+            if not use_cache:
+                raise ValueError("generate(lengths=...): ragged batches need use_cache")
+            lengths = [int(n) for n in lengths]
+            assert len(lengths) == B and all(1 <= n <= S for n in lengths)
+            if prefix is not None:
+                if prefix.batch not in (1, B):
+                    raise ValueError("generate(prefix=..., lengths=...): the prefix holds one row shared by every prompt, or one row per prompt")
+                self.cache = prefix.fork(rows=B, max_len=prefix.len + S + max_new_tokens)
+                _, h16 = self.lm.extend(emb, self.cache, lengths=lengths)
+            else:
+                self.cache = self.lm.new_cache(B, S + max_new_tokens, emb.device)
+                mask = (torch.arange(S)[None, :] < torch.tensor(lengths)[:, None]).long()
+                _, h16 = self.lm.prefill(emb, mask, cache=self.cache)
+            last = h16.view(B, S, -1)[torch.arange(B), torch.tensor(lengths) - 1].contiguous()
+            logits = self.m.logits_from(last, B, 1)[:, 0]
+            if self.rep > 1:
+                self.cache = self.cache.fork(rows=rows)
+                logits = logits.repeat_interleave(self.rep, dim=0)
+            self.logits = logits.float()
+        elif prefix is not None:
             # `prefix`: a KVCache holding the prompt's first positions (a prefilled video); inputs_embeds is the rest.  The work happens on a fork
             # — a copy of the prefix rows, made once per beam —, so the prefix itself stays as it was and serves the next call.
             if not use_cache or prefix.batch != B:
@@ -127,6 +164,8 @@ class _CacheStepper:
                 idx = beam_idx.to(self.cache.qkv[0].device)
                 for buf in self.cache.qkv:        # _reorder_cache: past.index_select(0, beam_idx), only the rows in use
                     buf[:, :n] = buf[:, :n].index_select(0, idx)
+                if self.cache.lens is not None:   # ragged: n = max(lens); the lengths travel with their rows (beams stay inside their prompt)
+                    self.cache.lens = [self.cache.lens[i] for i in beam_idx.tolist()]
             _, h16 = self.lm.decode_step(tok, self.cache)
             self.logits = self.m.logits_from(h16, next_tokens.numel(), 1)[:, 0].float()
         else:
@@ -139,16 +178,22 @@ class _CacheStepper:
 @torch.no_grad()
 def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sample=False, min_length=0, top_p=1.0,
              temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, stopping_criteria=None, eos_token_id=2,
-             pad_token_id=0, use_cache=True, generator=None, prefix=None):
+             pad_token_id=0, use_cache=True, generator=None, prefix=None, lengths=None, stop_sequences=None, return_lengths=False):
     """Returns the generated ids [B, n] (the prompt has no ids), HF semantics as described in the module docstring.
     prefix: a KVCache that already holds the first positions of every prompt (LlamaModel.prefill(cache=...) / Chat.prefill_video); `inputs_embeds` is then
-    the remainder of the prompt, appended behind it in one pass (LlamaModel.extend).  The prefix is left unchanged."""
+    the remainder of the prompt, appended behind it in one pass (LlamaModel.extend).  The prefix is left unchanged.
+    lengths: per-row token counts of a right-padded `inputs_embeds` (a ragged batch in one call; with a prefix the prefix may hold one shared row).
+    stop_sequences: list of 1-D id tensors — a row whose generated ids end in one of them is finished from that step on and emits pad_token_id, like a
+    row that emitted EOS (beam search: the prompt is closed when its first beam ends in one, its open beams become hypotheses).
+    return_lengths: also return the number of generated tokens per row (the rest of the row is padding)."""
     B = inputs_embeds.shape[0]
     dev = inputs_embeds.device
+    stop_sequences = list(stop_sequences) if stop_sequences else None
     if num_beams == 1:
-        st = _CacheStepper(lm_wrapper, inputs_embeds, B, max_new_tokens, use_cache, prefix)
+        st = _CacheStepper(lm_wrapper, inputs_embeds, B, max_new_tokens, use_cache, prefix, lengths)
         ids = torch.zeros((B, 0), dtype=torch.long, device=dev)
         unfinished = torch.ones(B, dtype=torch.long, device=dev)
+        n_gen = torch.zeros(B, dtype=torch.long, device=dev)
         while True:
             scores = _process_logits(st.logits.to(dev), ids, ids.shape[1], repetition_penalty, min_length, eos_token_id)
             if do_sample:
@@ -156,21 +201,24 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
                 nxt = torch.multinomial(probs, num_samples=1, generator=generator).squeeze(1)
             else:
                 nxt = scores.argmax(dim=-1)
-            if eos_token_id is not None:
+            if eos_token_id is not None or stop_sequences:
                 nxt = nxt * unfinished + pad_token_id * (1 - unfinished)
             ids = torch.cat([ids, nxt[:, None]], dim=-1)
+            n_gen = n_gen + unfinished
             if eos_token_id is not None:
                 unfinished = unfinished * (nxt != eos_token_id).long()
+            if stop_sequences:
+                unfinished = unfinished * (~_ends_in_stop(ids, stop_sequences)).long()
             if unfinished.max() == 0 or _stop(stopping_criteria, ids, scores) or ids.shape[1] >= max_new_tokens:
                 break
             st.advance(nxt)
         _check_exchanges(dev)
-        return ids
+        return (ids, n_gen.tolist()) if return_lengths else ids
 
     if do_sample:
         raise NotImplementedError("beam-sample is not used by the reference (demo: num_beams=5, do_sample=False)")
     nb = num_beams
-    st = _CacheStepper(lm_wrapper, inputs_embeds, B * nb, max_new_tokens, use_cache, prefix)
+    st = _CacheStepper(lm_wrapper, inputs_embeds, B * nb, max_new_tokens, use_cache, prefix, lengths)
     ids = torch.zeros((B * nb, 0), dtype=torch.long, device=dev)
     beam_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
     beam_scores[:, 1:] = -1e9
@@ -212,6 +260,14 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
         beam_scores = next_scores.view(-1)
         beam_idx = next_index.view(-1)
         ids = torch.cat([ids[beam_idx], next_tokens.view(-1, 1)], dim=-1)
+        if stop_sequences:
+            # per prompt what a stopping criterion does to a single prompt (it looks at the first row and ends the search): the open beams become hypotheses
+            hit = _ends_in_stop(ids, stop_sequences).tolist()
+            for b in range(B):
+                if not done[b] and hit[b * nb]:
+                    for j in range(nb):
+                        hyps[b].add(ids[b * nb + j].clone(), float(beam_scores[b * nb + j]))
+                    done[b] = True
         if all(done) or _stop(stopping_criteria, ids, None) or ids.shape[1] >= max_new_tokens:
             break
         st.advance(next_tokens.view(-1), beam_idx)
@@ -229,7 +285,7 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
         if len(o) < sent_max:
             res[b, len(o)] = eos_token_id
     _check_exchanges(dev)
-    return res
+    return (res, [min(len(o) + 1, sent_max) for o in out]) if return_lengths else res
 
 
 def _check_exchanges(dev):

@@ -27,7 +27,8 @@ EXPORTS = ["stllm_last_error", "stllm_abi_version", "stllm_last_kernel", "stllm_
            "stllm_vit_blocks_scratch_bytes", "stllm_vit_blocks", "stllm_llama_layers_scratch_bytes", "stllm_llama_layers", "stllm_llama_layer_sp_scratch_bytes", "stllm_llama_layer_sp",
            "stllm_qformer_layers_scratch_bytes", "stllm_qformer_layers", "stllm_split3_rows", "stllm_gemm_split_ws_bytes",
            "stllm_lora_down_workspace_bytes", "stllm_lora_down", "stllm_llama_layers_lora_scratch_bytes", "stllm_llama_layers_lora",
-           "stllm_attention_offset_workspace_bytes", "stllm_attention_offset", "stllm_llama_layers_extend", "stllm_gemv_w8"]
+           "stllm_attention_offset_workspace_bytes", "stllm_attention_offset", "stllm_llama_layers_extend", "stllm_gemv_w8",
+           "stllm_attention_decode_ragged_workspace_bytes", "stllm_attention_decode_ragged", "stllm_kv_append_rows"]
 
 
 def torch_dtype(d):
@@ -153,6 +154,10 @@ def _bind(L, strict=True):
     B("stllm_attention_decode_workspace_bytes", [c_int, c_int, c_int], c_int64)
     B("stllm_attention_decode", [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int,
                                  c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p])
+    B("stllm_attention_decode_ragged_workspace_bytes", [c_int, c_int, c_int], c_int64)
+    B("stllm_attention_decode_ragged", [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int,
+                                        c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_void_p])
+    B("stllm_kv_append_rows", [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
     B("stllm_gemm_profile", [c_int, c_char_p])
     B("stllm_gemm_profile_count", [])
     B("stllm_gemm_profile_read", [c_int, c_char_p, c_int, ctypes.POINTER(c_float), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)])
@@ -921,7 +926,8 @@ def attention(q, k, v, *, B, H, Sq, Skv, D, scale, causal=False, kv_len=None, ou
     """q/k/v: 2-D views [B*S, >=H*D] of the compute dtype (may be column slices of a fused QKV buffer).
     *_strides = (batch_stride, row_stride) in elements; default: rows of one batch are consecutive.
     q_off > 0 (stllm_attention_offset): query row i sits at position q_off + i — with `causal`, key j is visible iff j <= q_off + i (q_off + Sq <= Skv);
-    q_off = 0 is the call it always was."""
+    q_off = 0 is the call it always was.  Sq = 1 with a kv_len (a ragged KV cache: row b attends keys [0, kv_len[b]), Skv their upper bound) runs the ragged
+    decode kernels in bf16 / fp16 at D = 128 (attention_decode_ragged); fp32 keeps stllm_attention's kv_len route."""
     td = q.dtype
     if q_off:
         qs = q_strides if q_strides is not None else (Sq * q.stride(0), q.stride(0))
@@ -948,12 +954,48 @@ def attention(q, k, v, *, B, H, Sq, Skv, D, scale, causal=False, kv_len=None, ou
         _check(lib().stllm_attention_decode(dtype_code(td), _p(q), qs[0], _p(k), ks[0], ks[1], _p(v), vs[0], vs[1], _p(out),
                                             out.stride(0), B, H, Skv, D, scale, _p(ws), need, _stream()), "stllm_attention_decode")
         return out
+    if Sq == 1 and D == 128 and kv_len is not None and td in (torch.bfloat16, torch.float16) and _decode_attn:
+        return attention_decode_ragged(q, k, v, kv_len, B=B, H=H, max_kv=Skv, D=D, scale=scale, out=out, q_stride=qs[0], k_strides=ks, v_strides=vs)
     if kv_len is not None:
         _req(kv_len, torch.int32, "kv_len")
     _check(lib().stllm_attention(dtype_code(td), _p(q), qs[0], qs[1], _p(k), ks[0], ks[1], _p(v), vs[0], vs[1],
                                  _p(out), Sq * out.stride(0), out.stride(0), B, H, Sq, Skv, D, scale, int(causal),
                                  _p(kv_len), _stream()), "stllm_attention")
     return out
+
+
+def attention_decode_ragged(q, k, v, kv_len, *, B, H, max_kv, D, scale, out=None, q_stride=None, k_strides=None, v_strides=None):
+    """stllm_attention_decode_ragged: one query row per batch entry against a KV cache whose rows have their own lengths.  q: [B, >= H*D] (row stride
+    q_stride), k / v: 2-D views with (batch_stride, row_stride) in elements, kv_len: int32 [B] on the device, max_kv: the host-known bound of the lengths.
+    bf16 / fp16 at D = 128; anything else is an error (STLLM_ERR_UNSUPPORTED), not a fallback."""
+    td = q.dtype
+    _req(kv_len, torch.int32, "kv_len")
+    if kv_len.numel() != B:
+        raise RuntimeError(f"attention_decode_ragged: kv_len has {kv_len.numel()} entries for B = {B}")
+    ks = k_strides if k_strides is not None else (max_kv * k.stride(0), k.stride(0))
+    vs = v_strides if v_strides is not None else (max_kv * v.stride(0), v.stride(0))
+    if out is None:
+        out = torch.empty((B, H * D), device=q.device, dtype=td)
+    need = int(lib().stllm_attention_decode_ragged_workspace_bytes(B, H, max_kv))
+    if need < 0:
+        raise RuntimeError(f"stllm_attention_decode_ragged_workspace_bytes: bad shape (B={B}, H={H}, max_kv={max_kv})")
+    ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+    _check(lib().stllm_attention_decode_ragged(dtype_code(td), _p(q), q.stride(0) if q_stride is None else q_stride, _p(k), ks[0], ks[1], _p(v), vs[0], vs[1],
+                                               _p(out), out.stride(0), B, H, _p(kv_len), max_kv, D, scale, _p(ws), need, _stream()),
+           "stllm_attention_decode_ragged")
+    return out
+
+
+def kv_append_rows(src, cache, pos, *, with_q=False):
+    """stllm_kv_append_rows: cache[b, pos[b], cols] = src[b, cols] for the [k | v] columns (with_q: all of [q | k | v]) of the dense fused rows src [B, 3*hidden];
+    cache: [B, max_len, 3*hidden], pos: int32 [B] on the device (outside [0, max_len): a free slot, nothing written).  All compute dtypes."""
+    _req(src, cache.dtype, "src"); _req(pos, torch.int32, "pos")
+    B, max_len, D3 = cache.shape
+    if src.shape != (B, D3) or pos.numel() != B or cache.stride(2) != 1:
+        raise RuntimeError(f"kv_append_rows: src {tuple(src.shape)}, cache {tuple(cache.shape)}, pos {tuple(pos.shape)}")
+    _check(lib().stllm_kv_append_rows(dtype_code(cache.dtype), _p(src), src.stride(0), _p(cache), cache.stride(0), cache.stride(1), _p(pos), B, D3 // 3, max_len,
+                                      int(with_q), _stream()), "stllm_kv_append_rows")
+    return cache
 
 
 def gather_rows(src_a, idx_a, *, src_b=None, add=None, idx_add=None, out=None, scale=1.0):

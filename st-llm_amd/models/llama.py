@@ -103,13 +103,29 @@ def cfg_max_len(cfg):
 
 
 class KVCache:
-    """Per-layer fused [q | k | v] rows (compute dtype, k/q in the packed RoPE head layout).  Equal-length sequences only
-    (a clip, or the beams of one clip): right-padded batches would need per-row positions."""
+    """Per-layer fused [q | k | v] rows (compute dtype, k/q in the packed RoPE head layout).
+    `lens` is None for a UNIFORM cache — every row holds `len` positions (a clip, or the beams of one clip): the only kind there was, and its code paths
+    are untouched.  Otherwise the cache is RAGGED: `lens` is a host list of `batch` ints, row b holds positions [0, lens[b]) and `len` == max(lens), so
+    bounds checks against `len` keep their meaning.  prefill() with a right-padded mask and extend(lengths=) make a cache ragged; decode_step then appends
+    token b at position lens[b] (RoPE at that position) and row b attends its own lens[b] + 1 keys.  Rows behind lens[b] hold don't-care
+    values that later steps overwrite."""
 
     def __init__(self, n_layers, batch, max_len, hidden, dtype, device):
         self.max_len, self.batch, self.hidden = max_len, batch, hidden
         self.qkv = [torch.empty((batch, max_len, 3 * hidden), device=device, dtype=dtype) for _ in range(n_layers)]
         self.len = 0
+        self.lens = None
+
+    def set_lens(self, lens):
+        """per-row lengths (a list of `batch` ints) -> ragged; None, or all rows equal -> uniform"""
+        if lens is None or len(set(lens)) <= 1:
+            if lens is not None:
+                self.len = int(lens[0])
+            self.lens = None
+            return
+        lens = [int(n) for n in lens]
+        assert len(lens) == self.batch and min(lens) >= 0 and max(lens) <= self.max_len
+        self.lens, self.len = lens, max(lens)
 
     def fork(self, rows=None, max_len=None):
         """a new cache holding copies of the first `len` positions, every source row repeated rows // batch times (the beams of a prompt; a
@@ -122,12 +138,23 @@ class KVCache:
         for dst, src in zip(new.qkv, self.qkv):
             dst[:, :n] = src[:, :n].repeat_interleave(rep, dim=0) if rep > 1 else src[:, :n]
         new.len = n
+        if self.lens is not None:   # ragged: every copy of a row inherits its length
+            new.lens = [l for l in self.lens for _ in range(rep)]
         return new
 
     def truncate(self, n):
-        """forget the positions from n on (their rows are simply overwritten by the next extend / decode_step)"""
+        """forget the positions from n on (their rows are simply overwritten by the next extend / decode_step).  n: an int for every row, or a list with
+        one length per row (each at most what the row holds)"""
+        if isinstance(n, (list, tuple)):
+            have = self.lens if self.lens is not None else [self.len] * self.batch
+            assert len(n) == self.batch and all(0 <= int(a) <= h for a, h in zip(n, have))
+            self.set_lens(list(n))
+            return
         assert 0 <= n <= self.len
-        self.len = n
+        if self.lens is not None:
+            self.set_lens([min(l, n) for l in self.lens])
+        else:
+            self.len = n
 
 
 STACK_ENTRY = os.environ.get("STLLM_STACK_ENTRY", "1") != "0"   # 0: one C-ABI call per op instead of stllm_llama_layers / stllm_vit_blocks (A/B, tests)
@@ -241,18 +268,21 @@ class LlamaModel(nn.Module):
         dev = inputs_embeds.device
         x = inputs_embeds.reshape(B * S, D).float().clone()
         kv_len = None
+        row_lens = None
         if attention_mask is not None:
             m = hip.host_mask(attention_mask).long()   # the assembler built it on the host: no D2H read, no stall
             if not bool((m[:, 1:] <= m[:, :-1]).all()):
                 raise NotImplementedError("only right-padded attention masks occur on this path (st_llm.py:400-404)")
             if int(m.sum()) != m.numel():
-                kv_len = hip.h2d(m.sum(dim=1).to(torch.int32), dev)
+                row_lens = m.sum(dim=1).to(torch.int32)
+                kv_len = hip.h2d(row_lens, dev)
         cos, sin = self.rope(S, dev)
         if cache is not None:
-            if kv_len is not None:
-                raise NotImplementedError("KV cache needs equal-length sequences")
             assert cache.batch == B and cache.max_len >= S and cache.qkv[0].dtype == dt
             cache.len = S
+            # a right-padded batch fills a RAGGED cache: the fused rows land where they always do, kv_len masks the pad keys as on the no-cache path, the pad
+            # positions hold don't-care rows that later steps overwrite
+            cache.set_lens(row_lens.tolist() if row_lens is not None else None)
         # the 32-layer loop is ONE call into the C ABI (stllm_llama_layers; == prefill_layer_by_layer, bit for bit); with a cache the
         # fused QKV rows of every layer are written straight into its cache buffer (rows (b, s) at b * max_len + s)
         if cache is not None:
@@ -299,12 +329,14 @@ class LlamaModel(nn.Module):
             hip.gemm(g, pk["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
         return x
 
-    def extend(self, inputs_embeds, cache):
+    def extend(self, inputs_embeds, cache, lengths=None):
         """S new positions behind the P = cache.len positions the cache already holds, in ONE pass through the decoder layers (a question behind a
         prefilled video; forward(past_key_values=...) runs decode_step once per token instead).  inputs_embeds f32 [B,S,D].  Per layer: RMSNorm ->
         QKV GEMM + RoPE at the positions P .. P+S-1, written into rows [P, P+S) of the layer's cache buffer -> causal attention of the S query rows over
         the P+S cached keys with the query offset P (hip.attention(q_off=P)) -> o_proj -> MLP.  Sets cache.len = P + S; returns what prefill returns.
-        P = 0 is prefill(cache=cache).  bf16 / fp16 / fp32; the split modes (bf16x3 / mixed) are not wired."""
+        P = 0 is prefill(cache=cache).  bf16 / fp16 / fp32; the split modes (bf16x3 / mixed) are not wired.
+        lengths: suffixes of different lengths S_b <= S, right-padded to S, behind a uniform prefix — the cache becomes ragged (lens = P + S_b), the pad query
+        rows are don't-care.  Runs the per-op body on hip.attention(q_off=P, kv_len=P + S_b).  A ragged prefix takes one-token steps only (decode_step)."""
         cfg = self.config
         dt = runtime.compute_dtype()
         if runtime.gemm_split():
@@ -313,23 +345,36 @@ class LlamaModel(nn.Module):
         P = cache.len
         assert cache.batch == B and cache.qkv[0].dtype == dt
         assert P + S <= cache.max_len, "KV cache full"
+        if cache.lens is not None:
+            raise NotImplementedError("LlamaModel.extend behind a ragged prefix (rows of different lengths): append one token at a time with decode_step")
+        if lengths is not None:
+            lengths = [int(n) for n in lengths]
+            assert len(lengths) == B and all(1 <= n <= S for n in lengths)
+            if len(set(lengths)) == 1 and lengths[0] == S:
+                lengths = None
         if P == 0:
-            return self.prefill(inputs_embeds, None, cache=cache)
+            mask = None if lengths is None else (torch.arange(S)[None, :] < torch.tensor(lengths)[:, None]).long()
+            return self.prefill(inputs_embeds, mask, cache=cache)
         layers = self.pack(dt)
         H = cfg.num_attention_heads
         x = inputs_embeds.reshape(B * S, D).float().clone()
         cos, sin = self.rope(cache.max_len, inputs_embeds.device)
         cos, sin = cos[P:P + S], sin[P:P + S]
-        if STACK_ENTRY and "lora_A" not in layers[0]:
+        if lengths is not None:
+            kv_len = hip.h2d(torch.tensor([P + n for n in lengths], dtype=torch.int32), inputs_embeds.device)
+            self.extend_layers_per_op(x, layers, B, S, P, cos, sin, cache, dt, kv_len=kv_len)
+        elif STACK_ENTRY and "lora_A" not in layers[0]:
             hip.llama_layers_extend(x, layers, hip.llama_layer_array(layers, cache), B=B, S=S, pos0=P, n_heads=H, eps=cfg.rms_norm_eps, rope=(cos, sin),
                                     dtype=dt, cache=cache)
         else:
             self.extend_layers_per_op(x, layers, B, S, P, cos, sin, cache, dt)
         cache.len = P + S
+        if lengths is not None:
+            cache.set_lens([P + n for n in lengths])
         h16, h32 = hip.rmsnorm(x, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
         return h32.view(B, S, D), h16
 
-    def extend_layers_per_op(self, x, layers, B, S, P, cos, sin, cache, dt):
+    def extend_layers_per_op(self, x, layers, B, S, P, cos, sin, cache, dt, kv_len=None):
         """extend's layer loop as one C-ABI call per op — what stllm_llama_layers_extend issues from C (bit-identical), the body active LoRA adapters
         run, and the one the test-only CPU contract backend runs"""
         cfg = self.config
@@ -344,7 +389,7 @@ class LlamaModel(nn.Module):
             hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cos, sin), rope_seq=S, rope_cols=2 * D,
                      out=new, M=B * S, o_rows=(S, ML3), **_frag(pk, "wqkv"))
             a = hip.attention(new[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=S, Skv=P + S, D=hd, scale=hd ** -0.5, causal=True,
-                              q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D), v_strides=(ML3, 3 * D), q_off=P)
+                              q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D), v_strides=(ML3, 3 * D), q_off=P, **({"kv_len": kv_len} if kv_len is not None else {}))
             hip.gemm(a, pk["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
             h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
             g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, **_frag(pk, "wgu"))
@@ -467,6 +512,18 @@ class LlamaModel(nn.Module):
         assert pos < cache.max_len, "KV cache full"
         cos, sin = self.rope(cache.max_len, x_new.device)
         cpos, spos = cos[pos:pos + 1], sin[pos:pos + 1]
+        rs, rg = 1, None
+        if cache.lens is not None:
+            # ragged step: token b sits at position lens[b].  The RoPE epilogues take pos = row % rope_seq, so B table rows cos[lens[b]] with rope_seq = B
+            # need no GEMV change; the positions / lengths travel through the pinned ring (the host knows them: no device synchronisation).  The QKV
+            # GEMV writes rows at ONE stride only -> a dense [B, 3D] scratch row, scattered into the cache by kv_append_rows (decode_attn)
+            dev = x_new.device
+            assert cache.batch == B
+            pos_d = hip.h2d(torch.tensor(cache.lens, dtype=torch.int32), dev)
+            cpos, spos = hip.gather_rows(cos, pos_d), hip.gather_rows(sin, pos_d)
+            rs = B
+            rg = dict(pos=pos_d, kv_len=hip.h2d(torch.tensor([n + 1 for n in cache.lens], dtype=torch.int32), dev), max_kv=pos + 1,
+                      scratch=torch.empty((B, 3 * D), device=dev, dtype=dt))
         x = x_new.reshape(B, D).float().clone()
         ML3 = cache.max_len * 3 * D
         # 16-bit modes, <= 8 rows: both RMSNorms ride inside the GEMV that consumes them (2 launches per layer fewer)
@@ -474,22 +531,19 @@ class LlamaModel(nn.Module):
         #  the 5 rows of beam search, where 2752 workgroups x 6 staged rows re-read 0.5 GB through L2)
         fuse = dt != torch.float32 and B <= FUSE_NORM_ROWS
         for li_, pk in enumerate(layers):
-            row = cache.qkv[li_][:, pos]                                   # [B, 3D] view, row stride max_len*3D
+            row = cache.qkv[li_][:, pos] if rg is None else rg["scratch"]   # [B, 3D]: a view of the cache, row stride max_len*3D | the dense scratch
             if w8 is not None:   # the same step over the int8 weights (W8A16 kernels): same epilogues, same fused norms
-                self.decode_layer_w8(x, pk, w8[li_], row, cache, li_, pos, cpos, spos, fuse and B <= 2, dt)   # (stllm_gemv_w8 fuses the norm for <= 2 rows)
+                self.decode_layer_w8(x, pk, w8[li_], row, cache, li_, pos, cpos, spos, fuse and B <= 2, dt, rope_seq=rs, rg=rg)   # (stllm_gemv_w8 fuses the norm for <= 2 rows)
                 continue
             if "lora_A" in pk:   # active adapters: the fused-RMSNorm GEMV cannot see t = h A^T — norm, down projection, then the GEMV over K = D + P
-                hip.gemm(self.qkv_operand(x, pk, dt), pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=1, rope_cols=2 * D, out=row)
+                hip.gemm(self.qkv_operand(x, pk, dt), pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rs, rope_cols=2 * D, out=row)
             elif fuse:
-                hip.gemm(None, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=1, rope_cols=2 * D, out=row,
+                hip.gemm(None, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rs, rope_cols=2 * D, out=row,
                          a_norm=(x, pk["ln1"], cfg.rms_norm_eps))
             else:
                 h, _ = hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)
-                hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=1, rope_cols=2 * D, out=row)
-            full = cache.qkv[li_].view(B * cache.max_len, 3 * D)
-            a = hip.attention(row[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=1, Skv=pos + 1, D=hd,
-                              scale=hd ** -0.5, causal=False, q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D),
-                              v_strides=(ML3, 3 * D))
+                hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rs, rope_cols=2 * D, out=row)
+            a = self.decode_attn(row, cache, li_, pos, rg)
             hip.gemm(a, pk["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
             if fuse:
                 g = hip.gemm(None, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, a_norm=(x, pk["ln2"], cfg.rms_norm_eps))
@@ -497,27 +551,48 @@ class LlamaModel(nn.Module):
                 h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
                 g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU)
             hip.gemm(g, pk["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
-        cache.len = pos + 1
+        if rg is None:
+            cache.len = pos + 1
+        else:
+            cache.lens = [n + 1 for n in cache.lens]
+            cache.len = pos + 1
         h16, h32 = hip.rmsnorm(x, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
         return h32.view(B, 1, D), h16
 
-    def decode_layer_w8(self, x, pk, q8, row, cache, li_, pos, cpos, spos, fuse, dt):
+    def decode_attn(self, row, cache, li_, pos, rg=None):
+        """the attention half of one decode layer, shared by the 16-bit, int8-weight and LoRA steps.  row: the new tokens' fused [q | k | v] rows [B, 3D].
+        Uniform (rg None): row IS row `pos` of the layer's cache buffer, every batch row attends keys [0, pos].  Ragged (rg: decode_step's per-step
+        tables): row is the dense scratch — its [k | v] columns are scattered to position lens[b] of every cache row (one launch, kv_append_rows), then
+        q is read from the scratch and row b attends its own lens[b] + 1 cached keys (the ragged decode kernels; fp32: stllm_attention's kv_len)."""
+        B, D = row.shape[0], row.shape[1] // 3
+        H = self.config.num_attention_heads
+        hd = D // H
+        ML3 = cache.max_len * 3 * D
+        full = cache.qkv[li_].view(B * cache.max_len, 3 * D)
+        if rg is None:
+            return hip.attention(row[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=1, Skv=pos + 1, D=hd,
+                                 scale=hd ** -0.5, causal=False, q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D),
+                                 v_strides=(ML3, 3 * D))
+        # the cache rows behind a row's length are UNINITIALISED memory.  The ragged decode kernels and the fp32 vector kernel bound their key loops by
+        # kv_len and never read them; the 16-bit tile kernels load whole key tiles up to Skv and mask the scores only (0 x NaN would reach the output)
+        if row.dtype != torch.float32 and (hd != 128 or not hip._decode_attn):
+            raise NotImplementedError("ragged decode step in bf16 / fp16 needs the ragged decode attention kernels (head_dim 128, hip._decode_attn on)")
+        hip.kv_append_rows(row, cache.qkv[li_], rg["pos"])
+        return hip.attention(row[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=1, Skv=rg["max_kv"], D=hd,
+                             scale=hd ** -0.5, causal=False, kv_len=rg["kv_len"], q_strides=(3 * D, 3 * D), k_strides=(ML3, 3 * D),
+                             v_strides=(ML3, 3 * D))
+
+    def decode_layer_w8(self, x, pk, q8, row, cache, li_, pos, cpos, spos, fuse, dt, rope_seq=1, rg=None):
         """one decoder layer of decode_step with its four projections on hip.gemv_w8 (q8: pack_w8's entry of the layer); attention and norms as in the 16-bit step"""
         cfg = self.config
         B, D = x.shape
-        H = cfg.num_attention_heads
-        hd = D // H
-        ML3 = cache.max_len * 3 * D
         if fuse:
-            hip.gemv_w8(None, *q8["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=1, rope_cols=2 * D, out=row,
+            hip.gemv_w8(None, *q8["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rope_seq, rope_cols=2 * D, out=row,
                         a_norm=(x, pk["ln1"], cfg.rms_norm_eps))
         else:
             h, _ = hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)
-            hip.gemv_w8(h, *q8["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=1, rope_cols=2 * D, out=row)
-        full = cache.qkv[li_].view(B * cache.max_len, 3 * D)
-        a = hip.attention(row[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=1, Skv=pos + 1, D=hd,
-                          scale=hd ** -0.5, causal=False, q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D),
-                          v_strides=(ML3, 3 * D))
+            hip.gemv_w8(h, *q8["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rope_seq, rope_cols=2 * D, out=row)
+        a = self.decode_attn(row, cache, li_, pos, rg)
         hip.gemv_w8(a, *q8["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
         if fuse:
             g = hip.gemv_w8(None, *q8["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, a_norm=(x, pk["ln2"], cfg.rms_norm_eps))

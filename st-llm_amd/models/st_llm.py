@@ -787,15 +787,53 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
     @torch.no_grad()
     def generate(self, inputs_embeds=None, max_new_tokens=16, num_beams=1, do_sample=False, stopping_criteria=None,
                  attention_mask=None, use_cache=True, min_length=0, top_p=1.0, repetition_penalty=1.0, length_penalty=1.0,
-                 temperature=1.0, eos_token_id=2, pad_token_id=0, generator=None, prefix_cache=None, **unused):
+                 temperature=1.0, eos_token_id=2, pad_token_id=0, generator=None, prefix_cache=None, batching="groups", stop_sequences=None,
+                 return_lengths=False, **unused):
         """`llama_model.generate(inputs_embeds=..., ...)` as Chat.answer calls it (conversation.py:231-243; demo.py runs
         num_beams=5, do_sample=False): HIP prefill of `inputs_embeds` into a KV cache, then one decode step per token with
         HF's greedy / sampling / beam-search bookkeeping restated in stllm_amd/generation.py.  eos / pad default to the
         Vicuna generation config (2 / 0).  A padded batch (attention_mask rows of different valid lengths, left- or right-padded) is generated by length groups
         (see below).  Returns the generated ids [B, n] (the prompt has no ids).
         prefix_cache: a KVCache holding the first positions of the prompt (Chat.prefill_video); `inputs_embeds` is then the rest of the prompt only, and
-        the prefix is left unchanged for the next call.  One prompt x beams, as the reference sends: ragged batches reject it."""
+        the prefix is left unchanged for the next call.  Under batching="groups" it serves one prompt x beams (or equal-length prompts), as the reference
+        sends: a padded batch rejects it; batching="ragged" accepts both together (below).
+        batching: "groups" (default) serves a padded batch by length groups, one decode loop per distinct length; "ragged" serves it in ONE batched call on a
+        ragged KV cache (KVCache.lens) — every row still generates exactly as its unpadded prompt would alone.  Left-padded rows are shifted
+        to right-padded first.  With prefix_cache the prefix may hold one row shared by all prompts (N questions about one video) or one row per prompt.
+        stop_sequences / return_lengths: see generation.generate (per-row stop; the number of generated tokens per row)."""
         from .. import generation
+        if batching not in ("groups", "ragged"):
+            raise ValueError(f"generate(batching={batching!r}): 'groups' or 'ragged'")
+        if batching == "ragged":
+            B, S = inputs_embeds.shape[:2]
+            lengths = None
+            if attention_mask is not None:
+                m = hip.host_mask(attention_mask).to(torch.bool)
+                lengths = m.sum(dim=1).tolist()
+                if min(lengths) < 1:
+                    raise ValueError("generate(batching='ragged'): every prompt needs at least one token")
+                if not bool(m.all()):
+                    right = m.long()
+                    right = bool((right[:, 1:] <= right[:, :-1]).all())
+                    if not right:   # left-padded rows (or a mix): shift every row's tokens to the front — positions count real tokens only
+                        emb = torch.zeros_like(inputs_embeds)
+                        for b, n in enumerate(lengths):
+                            first = int(m[b].long().argmax())
+                            if not bool(m[b, first:first + n].all()):
+                                raise NotImplementedError("generate(batching='ragged'): the tokens of a row must be contiguous (left- or right-padded)")
+                            emb[b, :n] = inputs_embeds[b, first:first + n]
+                        inputs_embeds = emb
+                    inputs_embeds = inputs_embeds[:, :max(lengths)]
+                if len(set(lengths)) == 1 and lengths[0] == inputs_embeds.shape[1] and (prefix_cache is None or prefix_cache.batch == B):
+                    lengths = None   # equal lengths: the plain batched call
+            if lengths is None and prefix_cache is not None and prefix_cache.batch != B:
+                lengths = [inputs_embeds.shape[1]] * B   # one shared prefix row, equal-length questions: the ragged stepper forks it per prompt
+            return generation.generate(self, inputs_embeds, max_new_tokens=max_new_tokens, num_beams=num_beams, do_sample=do_sample,
+                                       min_length=min_length, top_p=top_p, temperature=temperature,
+                                       repetition_penalty=repetition_penalty, length_penalty=length_penalty,
+                                       stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                                       use_cache=use_cache, generator=generator, prefix=prefix_cache, lengths=lengths,
+                                       stop_sequences=stop_sequences, return_lengths=return_lengths)
         if attention_mask is not None and inputs_embeds.shape[0] > 1:
             if prefix_cache is not None and not bool(hip.host_mask(attention_mask).to(torch.bool).all()):
                 raise NotImplementedError("generate(prefix_cache=...) with a padded batch: a prefix serves equal-length prompts only")
@@ -828,7 +866,8 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
                                    min_length=min_length, top_p=top_p, temperature=temperature,
                                    repetition_penalty=repetition_penalty, length_penalty=length_penalty,
                                    stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                                   use_cache=use_cache, generator=generator, prefix=prefix_cache)
+                                   use_cache=use_cache, generator=generator, prefix=prefix_cache, stop_sequences=stop_sequences,
+                                   return_lengths=return_lengths)
 
     @classmethod
     def get_state_dict(cls, path, prefix="pytorch_model"):

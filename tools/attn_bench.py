@@ -14,6 +14,49 @@ if "--probe" in sys.argv:   # how does the Llama prefill kernel's time scale wit
 AUDIT = "--audit" in sys.argv   # the Llama prefill kernel's work split (query tiles per workgroup x waves per query tile) forced through option attn_dma = 10 nw + ks
 if AUDIT:
     CASES = [(f"llama_S{S}_B{B}", B, 32, S, S, 128, True, 32) for B, S in ((1, 178), (1, 296), (1, 400), (1, 528), (1, 576), (1, 700), (1, 1088), (4, 576), (2, 576), (16, 576))]
+if "--ragged" in sys.argv:
+    # one-token decode attention over a ragged KV cache (B = 8, mixed lengths up to ~1100, and one case beyond the single-pass limit): the ragged kernels against
+    # the uniform decode kernels with EVERY row at the maximum length, and the append scatter; same buffers, alternating, a captured graph of 20 calls per timing.
+    def timed_g(fn, rounds=5):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(20):
+                fn()
+        g.replay(); torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        best = float("inf")
+        for _ in range(rounds):
+            s.record(); g.replay(); e.record(); torch.cuda.synchronize()
+            best = min(best, s.elapsed_time(e) / 20 * 1e3)
+        return best
+    H, D = 32, 128
+    for lens in ([1100, 640, 333, 1021, 87, 590, 12, 845], [580] * 8, [2040, 700, 1500, 90], [601, 580, 577, 590, 600]):
+        B, L = len(lens), max(lens)
+        ML = L + 8
+        dt = torch.bfloat16
+        buf = torch.randn(B * ML, 3 * H * D, device="cuda").to(dt)
+        row = torch.randn(B, 3 * H * D, device="cuda").to(dt)
+        st = (ML * 3 * H * D, 3 * H * D)
+        kv_len = torch.tensor(lens, dtype=torch.int32).cuda()
+        pos = torch.tensor([n - 1 for n in lens], dtype=torch.int32).cuda()
+        out = torch.empty(B, H * D, device="cuda", dtype=dt)
+        kw = dict(B=B, H=H, Sq=1, Skv=L, D=D, scale=D ** -0.5, q_strides=(3 * H * D, 3 * H * D), k_strides=st, v_strides=st, out=out)
+        uni = lambda: hip.attention(row[:, :H * D], buf[:, H * D:2 * H * D], buf[:, 2 * H * D:], **kw)
+        rag = lambda: hip.attention(row[:, :H * D], buf[:, H * D:2 * H * D], buf[:, 2 * H * D:], kv_len=kv_len, **kw)
+        app = lambda: hip.kv_append_rows(row, buf.view(B, ML, 3 * H * D), pos)
+        res = {}
+        for rnd in range(2):
+            for name, f in (("uniform", uni), ("ragged", rag), ("append", app)):
+                res.setdefault(name, []).append(timed_g(f))
+        rag()
+        kern = hip.lib().stllm_last_kernel().decode()
+        print(f"decode attention B={B} lens={','.join(map(str, lens))}: uniform@{L} {min(res['uniform']):6.1f} us ({res['uniform'][0]:.1f} {res['uniform'][1]:.1f})  "
+              f"ragged {min(res['ragged']):6.1f} us ({res['ragged'][0]:.1f} {res['ragged'][1]:.1f})  kv_append_rows {min(res['append']):5.1f} us ({res['append'][0]:.1f} {res['append'][1]:.1f})"
+              f"  keys read {sum(lens)} vs {B * L}  -> {kern}", flush=True)
+    sys.exit(0)
 if "--suffix" in sys.argv:
     # LlamaModel.extend's shape: Sq new rows behind q_off cached ones, operands addressed inside one fused cache buffer as the model passes them.
     # The offset tile kernel (attn_ksplit = 0) and the key-split pair (1) on the same buffers, same process, alternating; "auto" is the dispatch rule.

@@ -15,6 +15,9 @@ ap.add_argument("--rows", type=int, default=1, help="sequences decoded together 
 ap.add_argument("--weights", choices=["16", "int8"], default="16", help="decode weights: the 16-bit pack, or its int8 copy on the W8A16 kernels (runtime.set_decode_weights)")
 ap.add_argument("--gemv", type=int, default=-1, help="stllm_set_option('gemm_gemv'): -1 default (M <= 8), 1 = M <= 4, 0 off")
 ap.add_argument("--attn-single", type=int, default=1, help="stllm_set_option('attn_decode_single')")
+ap.add_argument("--ragged", default="", help="L1,L2,...: time ragged steps at these per-row cache lengths against uniform steps with every row at max(L), alternating")
+ap.add_argument("--questions", default="", help="L1,L2,...: N questions of these lengths behind one prefilled 576-token prefix — generate(batching='ragged') in one "
+                                                "batch against one generate() per question (what a padded batch behind a prefix costs without the ragged cache)")
 args = ap.parse_args()
 torch.set_grad_enabled(False)
 dev = torch.device("cuda:0")
@@ -26,6 +29,81 @@ from stllm_amd import runtime
 runtime.set_decode_weights("int8" if args.weights == "int8" else None)
 hip.set_option("gemm_gemv", args.gemv)
 hip.set_option("attn_decode_single", args.attn_single)
+
+
+def ragged_steps(lens):
+    """ms per step, ragged cache at `lens` vs uniform cache with every row at max(lens): blocks of `--tokens` steps, alternating, 5 blocks each, medians.
+    Every step is undone (truncate) so that each one runs at the same lengths."""
+    R, L = len(lens), max(lens)
+    e = (torch.randn(R, L, 4096, device=dev) * 0.02)
+    uni = lm.new_cache(R, L + 8, dev)
+    lm.prefill(e, None, cache=uni)
+    rag = uni.fork()
+    rag.truncate(list(lens))
+    if rag.lens is None:
+        rag.lens = list(lens)
+    tok = torch.randn(R, 1, 4096, device=dev) * 0.02
+
+    def block(cache, keep):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.tokens):
+            _, h = lm.decode_step(tok, cache)
+            model.logits_from(h, R, 1)
+            cache.truncate(keep)
+            if isinstance(keep, list) and cache.lens is None:
+                cache.lens = list(keep)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.tokens * 1e3
+    for _ in range(2):
+        block(uni, L), block(rag, list(lens))
+    tu, tr = [], []
+    for _ in range(5):
+        tu.append(block(uni, L))
+        tr.append(block(rag, list(lens)))
+    mu, mr = sorted(tu)[2], sorted(tr)[2]
+    print(f"ragged decode ({R} rows, lens {','.join(map(str, lens))}, weights {args.weights}): uniform@{L} {mu:.3f} ms/step (blocks {' '.join(f'{x:.3f}' for x in tu)}), "
+          f"ragged {mr:.3f} ms/step (blocks {' '.join(f'{x:.3f}' for x in tr)}), ragged - uniform {mr - mu:+.3f} ms = {(mr - mu) / len(lm.layers) * 1e3:+.1f} us/layer")
+
+
+def questions_e2e(lens):
+    """tokens/s of N questions behind one prefilled prefix: one ragged batch vs one generate() per question; eos disabled so that both emit N x tokens ids"""
+    N, P = len(lens), 576
+    video = torch.randn(1, P, 4096, device=dev) * 0.02
+    prefix = lm.new_cache(1, P, dev)
+    lm.prefill(video, None, cache=prefix)
+    qs = [torch.randn(n, 4096, device=dev) * 0.02 for n in lens]
+    emb = torch.zeros(N, max(lens), 4096, device=dev)
+    mask = torch.zeros(N, max(lens), dtype=torch.long)
+    for i, q in enumerate(qs):
+        emb[i, :lens[i]] = q
+        mask[i, :lens[i]] = 1
+    kw = dict(max_new_tokens=args.tokens, eos_token_id=None, prefix_cache=prefix)
+
+    def one_batch():
+        return model.generate(inputs_embeds=emb, attention_mask=mask, batching="ragged", **kw)
+
+    def per_question():
+        return [model.generate(inputs_embeds=q[None], **kw) for q in qs]
+    res = {}
+    for name, f in (("ragged", one_batch), ("per-question", per_question)) * 3:   # alternating; the first round warms up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        res.setdefault(name, []).append(time.perf_counter() - t0)
+    for name, ts in res.items():
+        t = min(ts[1:])
+        print(f"{N} questions (lens {','.join(map(str, lens))}) behind a {P}-token prefix, {args.tokens} new tokens each [{name}]: {t * 1e3:.1f} ms "
+              f"= {N * args.tokens / t:.1f} tok/s (runs {' '.join(f'{x * 1e3:.1f}' for x in ts)})")
+
+
+if args.ragged:
+    ragged_steps([int(x) for x in args.ragged.split(",")])
+    sys.exit(0)
+if args.questions:
+    questions_e2e([int(x) for x in args.questions.split(",")])
+    sys.exit(0)
 R = args.rows
 emb = (torch.randn(1, S, 4096, device=dev) * 0.02).expand(R, S, 4096).contiguous()
 cache = lm.new_cache(R, S + args.tokens + 8, dev)
