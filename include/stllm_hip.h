@@ -376,6 +376,26 @@ int stllm_attention_decode_ragged(int dtype, const void* q, int64_t q_bs, const 
                                   void* stream);
 
 /*
+ * Shared-prefix attention (additive to ABI 7): B = G * R query rows in G contiguous groups of R.  Query (b, i) sees ALL P keys of prefix row b / R
+ * (kp / vp: G rows, read-only) and suffix key j of its own row b (ks / vs: B rows) iff j < min(sfx_len[b], max_sfx) — with `causal` also j <= sfx_q_off + i.
+ * sfx_len: int32 [B] in device memory, or NULL (every row holds max_sfx keys).  The prefix and the suffix buffers have independent (batch, row) strides, in
+ * elements; q, out: element (b, i, h, d) at b*bs + i*rs + h*128 + d.  Neither buffer is read at or behind those bounds (the rows there may be uninitialised).
+ *   bf16 / fp16, Sq == 1 (the decode step): a partial pass — prefix workgroups that load each K / V tile once for all R rows of a group (matrix cores) plus
+ *     suffix workgroups in the same launch — and a merge in a fixed order: two launches, deterministic.
+ *   bf16 / fp16, Sq > 1: the key-split tile kernels of stllm_attention_offset, once over the prefix (batch G, R * Sq query rows) and once per row over the
+ *     suffix, then the same merge.  Needs the query rows of a group at one row stride (q_bs == Sq * q_rs) when R > 1.
+ *   fp32: one vector kernel (the verify mode), any Sq.
+ * head_dim 128 only; anything unsupported returns STLLM_ERR_UNSUPPORTED (stllm_last_error() says what): nothing else runs in its place.
+ * workspace: >= stllm_attention_shared_workspace_bytes(B, G, H, Sq, P, max_sfx) bytes, 16-byte aligned, no initialisation needed (unused in fp32).
+ */
+int64_t stllm_attention_shared_workspace_bytes(int B, int G, int H, int Sq, int P, int max_sfx);
+int stllm_attention_shared(int dtype, const void* q, int64_t q_bs, int64_t q_rs, const void* kp, int64_t kp_bs, int64_t kp_rs,
+                           const void* vp, int64_t vp_bs, int64_t vp_rs, int P, const void* ks, int64_t ks_bs, int64_t ks_rs,
+                           const void* vs, int64_t vs_bs, int64_t vs_rs, const int32_t* sfx_len, int max_sfx, int sfx_q_off,
+                           void* out, int64_t o_bs, int64_t o_rs, int B, int G, int H, int Sq, int D, float scale, int causal,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
  * Ragged KV-cache append (additive to ABI 7): for every batch row b the [k | v] columns (with_q != 0: [q | k | v]) of the dense fused row
  * src[b*ld_src .. + 3*hidden) are copied to cache[b*batch_stride + pos[b]*row_stride + the same columns].  pos: int32 [B] in device memory; a position
  * outside [0, max_len) marks a free slot: nothing is written for that row.  All strides in elements of `dtype` (bf16 / fp16 / fp32).  16-byte vector

@@ -90,12 +90,13 @@ class Chat:
 
     def answer(self, img_list, question_ids, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9,
                repetition_penalty=1.0, length_penalty=1, temperature=1.0, max_length=2000, do_sample=False,
-               stopping_criteria=None, instruction=False, prefix=None, **kw):
+               stopping_criteria=None, instruction=False, prefix=None, share_prefix=False, **kw):
         """conversation.py:213-253: keep the last `max_length - max_new_tokens` embeddings, generate with the reference's
         knobs (demo.py: num_beams=5, do_sample=False), drop a leading <unk> (0) / <s> (1) token.  prefix: a prefill_video(img_list) result — the
         video's K / V rows are reused and only [BOS] + question is run (same ids; see prefill_video for the text-conditioned case).  This entry point is the
         `get_context_emb_sim` path (no conv.instruction: video tokens + question), for which the reference OVERRIDES
-        repetition_penalty with 1.5 (conversation.py:219-220) whatever the caller passed; instruction=True keeps the argument."""
+        repetition_penalty with 1.5 (conversation.py:219-220) whatever the caller passed; instruction=True keeps the argument.
+        share_prefix: the beams read one copy of the prompt's (or the video prefix's) K / V rows (generate(share_prefix=True))."""
         embs, att = self.get_context_emb_ids(img_list, question_ids)
         if not instruction:
             repetition_penalty = 1.5
@@ -109,7 +110,8 @@ class Chat:
             stopping_criteria = self.stopping_criteria
         out = self.LLM.generate(inputs_embeds=embs, max_new_tokens=max_new_tokens, stopping_criteria=stopping_criteria,
                                 num_beams=num_beams, do_sample=do_sample, min_length=min_length, top_p=top_p,
-                                repetition_penalty=repetition_penalty, length_penalty=length_penalty, temperature=temperature, **kw)
+                                repetition_penalty=repetition_penalty, length_penalty=length_penalty, temperature=temperature,
+                                share_prefix=share_prefix, **kw)
         hip.gemm_workspace_check(embs.device, wait=True) if embs.is_cuda else None   # generate() synchronised on every token anyway
         tok = out[0]
         if tok.numel() and int(tok[0]) == 0:   # conversation.py:246-249
@@ -120,11 +122,12 @@ class Chat:
 
     def answer_many(self, img_list, questions_ids, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9,
                     repetition_penalty=1.0, length_penalty=1, temperature=1.0, max_length=2000, do_sample=False,
-                    stop_sequences=None, instruction=False, prefix=None, **kw):
+                    stop_sequences=None, instruction=False, prefix=None, share_prefix=False, **kw):
         """N questions about ONE video in one ragged batch (generate(batching="ragged")): answer()'s truncation rule and its repetition_penalty = 1.5
         override per question, Chat's stop tokens as per-row stop_sequences (a row that ends in '###' is finished, the others go on).  prefix: a
         prefill_video(img_list) result — the video is prefilled once, forked to the N rows, and only [BOS] + question runs per row.  Returns one
-        (text, ids) pair per question, each what answer() returns for that question alone."""
+        (text, ids) pair per question, each what answer() returns for that question alone.  share_prefix: the N rows (and their beams) read the prefilled video
+        where it is instead of a fork each (generate(share_prefix=True))."""
         pairs = [self.get_context_emb_ids(img_list, q) for q in questions_ids]
         if not instruction:
             repetition_penalty = 1.5
@@ -145,7 +148,7 @@ class Chat:
         out, n_out = self.LLM.generate(inputs_embeds=batch, attention_mask=mask, max_new_tokens=max_new_tokens, stop_sequences=stop_sequences,
                                        num_beams=num_beams, do_sample=do_sample, min_length=min_length, top_p=top_p, batching="ragged",
                                        repetition_penalty=repetition_penalty, length_penalty=length_penalty, temperature=temperature,
-                                       return_lengths=True, **kw)
+                                       return_lengths=True, share_prefix=share_prefix, **kw)
         hip.gemm_workspace_check(batch.device, wait=True) if batch.is_cuda else None
         res = []
         for row, n in zip(out, n_out):

@@ -70,7 +70,10 @@ __device__ __forceinline__ void attn_block_coords(int& chunk_x, int& h, int& b) 
 // [range * kps, (range + 1) * kps) only and leaves the un-normalised fp32 state (O[128], m, l) of every query row in p.ws for attn_ksplit_merge_kernel.
 constexpr int kSplRec = 132;   // floats per partial record: O[128], m (raw-score maximum), l, 2 pad (16-byte aligned records)
 
-template <typename T, int DP, int NW, bool SPLIT = false>
+// LIVE (the suffix pass of stllm_attention_shared only): key rows at or behind the batch row's kv_len are not LOADED (zeros instead) — the rows behind a
+// suffix's length are uninitialised memory, and a masked score of 0 times a NaN in V would reach the output.  Every other instantiation has LIVE = false
+// and compiles to what it always was.
+template <typename T, int DP, int NW, bool SPLIT = false, bool LIVE = false>
 __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) {
   constexpr int KS = DP / 16;          // k-steps of the S^T MFMA chain
   constexpr int DB = DP / 32;          // 32-row blocks of O^T
@@ -128,7 +131,7 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
       const int ch = tid + c * NT;
       const int cc = ch >> 5, row = ch & 31;   // consecutive lanes = consecutive keys: conflict-free transposed V writes
       const int kv = kv0 + row;
-      const bool ok = (ch < NCH) && (kv < p.Skv) && (cc * 8 < D);
+      const bool ok = (ch < NCH) && (kv < (LIVE ? kvlen : p.Skv)) && (cc * 8 < D);
       i32x4 z = {0, 0, 0, 0};
       kreg[c] = ok ? *reinterpret_cast<const i32x4*>(kbase + ((int64_t)kv * p.k_rs + cc * 8) * 2) : z;
       vreg[c] = ok ? *reinterpret_cast<const i32x4*>(vbase + ((int64_t)kv * p.v_rs + cc * 8) * 2) : z;
@@ -1851,6 +1854,482 @@ extern "C" int stllm_attention_decode_ragged(int dtype, const void* q, int64_t q
   }
   STLLM_CHECK_LAUNCH("stllm_attention_decode_ragged");
   return STLLM_OK;
+}
+
+// =====================================================================================================
+// Shared-prefix attention: B = G * R query rows in G contiguous groups; the R rows of group g read the SAME P prefix keys (row g of
+// the prefix buffers, never written) and each row b its own suffix keys [0, sfx_len[b]) (row b of the suffix buffers).
+//   decode (Sq = 1, 16-bit): attn_shared_decode_kernel + attn_shared_merge_kernel, two launches.
+//     prefix workgroups — one per (g, h, 32-row query tile, key range): 4 waves on disjoint 32-key tiles of the range (wave w: tiles w, w + 4, ...).  A wave
+//       loads a K / V tile ONCE and applies it to all (<= 32) queries of the tile on the matrix cores: S^T = K . Q^T with the K rows as the A operand straight
+//       from global memory (lane = key row: the fragment a lane needs is 16 contiguous bytes of its row), V^T through a wave-private LDS tile (the transposed
+//       store of attn_mfma_kernel), the online softmax of attn_mfma_kernel per lane (= per query).  The next tile's loads are issued between the S^T chain
+//       and the softmax.  Keys at or behind P are neither loaded nor counted.  The four wave states merge through LDS in a fixed order (2 <- 3 | 0 <- 1 ... see
+//       below) and leave ONE record per (query row, range).
+//     suffix workgroups — further blockIdx.x values of the same launch: the loop of decode_partial_body over keys [s * kps_s, ...) of row b's own suffix
+//       (VALU; a copy, because the record layout differs and the ragged kernels' instruction streams are not to change).
+//     records: kSplRec floats, O[128] | m | l, with m in the LOG2 domain (raw maximum * scale * log2 e) in this path.
+//   extend (Sq > 1, 16-bit): attn_mfma_kernel<T, 128, NW, SPLIT> twice — the prefix as a non-causal problem of batch G with R * Sq query rows, the suffix
+//     per row (causal, q_off = sfx_q_off, kv_len = sfx_len, LIVE loads) — and the same merge (their records keep RAW maxima: m_mult = scale * log2 e).
+//   fp32 (verify mode, any Sq): attn_shared_f32_kernel, one workgroup per (b, i, h), a two-source key loop on the VALU.
+// The merge folds a query row's prefix ranges, then its suffix records, in ascending order: deterministic, no atomics, no flags.
+// =====================================================================================================
+namespace {
+
+struct SharedParams {
+  const char* q; int64_t q_bs, q_rs;
+  const char* kp; int64_t kp_bs, kp_rs;
+  const char* vp; int64_t vp_bs, vp_rs;
+  const char* ks; int64_t ks_bs, ks_rs;
+  const char* vs; int64_t vs_bs, vs_rs;
+  char* o; int64_t o_bs, o_rs;
+  const int32_t* sfx_len;
+  int max_sfx, sfx_q_off;
+  int B, G, R, H, Sq, P;
+  float scale_log2;
+  int causal;
+  float* ws_p; float* ws_s;             // prefix records [G][H][R * Sq][n_p], suffix records [B][H][Sq][n_s]
+  int nsp, kps, qtiles, nss, kps_s;     // decode plan (shared_plan)
+  float m_mult;                         // merge: log2-domain maximum = record maximum * m_mult
+};
+
+// key ranges of the decode pass: a pure function of (G, H, R, P) / of max_sfx, shared by the workspace query and the launch.  Prefix ranges are whole
+// 32-key tiles, four tiles (one per wave) or more each, at most 32 ranges, enough of them for ~512 workgroups; suffix ranges hold ~64 keys, at most 8.
+struct SharedPlan { int nsp, kps, qtiles, nss, kps_s; };
+SharedPlan shared_plan(int G, int H, int R, int P, int max_sfx) {
+  SharedPlan pl;
+  pl.qtiles = (R + 31) / 32;
+  const int tiles = (P + 31) / 32;
+  const int64_t wgs = (int64_t)G * H * pl.qtiles;
+  int want = (int)((512 + wgs - 1) / wgs);
+  if (want > 32) want = 32;
+  if (want > (tiles + 3) / 4) want = (tiles + 3) / 4;
+  if (want < 1) want = 1;
+  const int tps = (tiles + want - 1) / want;
+  pl.kps = tps * 32;
+  pl.nsp = (tiles + tps - 1) / tps;
+  int ns = (max_sfx + 63) / 64;
+  pl.nss = ns < 1 ? 1 : (ns > 8 ? 8 : ns);
+  pl.kps_s = (max_sfx + pl.nss - 1) / pl.nss;
+  if (pl.kps_s < 1) pl.kps_s = 1;
+  return pl;
+}
+
+constexpr int kShVPitch = 32 * 2 + 8;                  // bytes per V^T row of a wave's LDS tile (attn_mfma_kernel's VPITCH)
+constexpr int kShLds = 4 * kDecD * kShVPitch;          // 36864 bytes: four wave-private V^T tiles; reused by the wave merge (2 x 66 x 64 floats) and the suffix body
+
+template <typename T>
+__device__ __forceinline__ void shared_suffix_body(const SharedParams& p, float* __restrict__ lds_f, int b, int h, int sp) {
+  float (*part)[kSplRec] = reinterpret_cast<float (*)[kSplRec]>(lds_f);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int len = p.sfx_len ? min(p.sfx_len[b], p.max_sfx) : p.max_sfx;
+  if (p.causal) len = min(len, p.sfx_q_off + 1);
+  const int k0 = sp * p.kps_s, k1 = min(len, k0 + p.kps_s);
+  float q0, q1;
+  widen2<T>(*reinterpret_cast<const uint32_t*>(p.q + ((int64_t)b * p.q_bs + (int64_t)h * kDecD + 2 * lane) * 2), q0, q1);
+  q0 *= p.scale_log2;
+  q1 *= p.scale_log2;
+  const char* kb = p.ks + ((int64_t)b * p.ks_bs + (int64_t)h * kDecD + 2 * lane) * 2;
+  const char* vb = p.vs + ((int64_t)b * p.vs_bs + (int64_t)h * kDecD + 2 * lane) * 2;
+  float m = kNeg, l = 0.0f, o0 = 0.0f, o1 = 0.0f;
+  for (int key = k0 + wave; key < k1; key += 4) {
+    float ka, kc, va, vc;
+    widen2<T>(*reinterpret_cast<const uint32_t*>(kb + (int64_t)key * p.ks_rs * 2), ka, kc);
+    widen2<T>(*reinterpret_cast<const uint32_t*>(vb + (int64_t)key * p.vs_rs * 2), va, vc);
+    const float s = wave_sum(fmaf(q0, ka, q1 * kc));   // log2-domain score, identical in every lane
+    const float mn = fmaxf(m, s);
+    const float alpha = __builtin_amdgcn_exp2f(m - mn), pr = __builtin_amdgcn_exp2f(s - mn);
+    l = fmaf(l, alpha, pr);
+    o0 = fmaf(o0, alpha, pr * va);
+    o1 = fmaf(o1, alpha, pr * vc);
+    m = mn;
+  }
+  if (lane == 0) { part[wave][128] = m; part[wave][129] = l; }
+  part[wave][2 * lane] = o0;
+  part[wave][2 * lane + 1] = o1;
+  __syncthreads();
+  if (wave == 0) {
+    const float mm = fmaxf(fmaxf(part[0][128], part[1][128]), fmaxf(part[2][128], part[3][128]));
+    float ll = 0.0f, a0 = 0.0f, a1 = 0.0f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float f = __builtin_amdgcn_exp2f(part[w][128] - mm);   // a wave without keys: exp2(-huge) == 0 (all four empty: 1 * 0)
+      ll = fmaf(part[w][129], f, ll);
+      a0 = fmaf(part[w][2 * lane], f, a0);
+      a1 = fmaf(part[w][2 * lane + 1], f, a1);
+    }
+    float* rec = p.ws_s + (((int64_t)b * p.H + h) * p.nss + sp) * kSplRec;
+    rec[2 * lane] = a0;
+    rec[2 * lane + 1] = a1;
+    if (lane == 0) { rec[128] = mm; rec[129] = ll; }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attn_shared_decode_kernel(const SharedParams p) {
+  __shared__ __attribute__((aligned(16))) char lds[kShLds];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 31, lh = lane >> 5;
+  const int n_prefix = p.G * p.H * p.qtiles * p.nsp;
+  int id = blockIdx.x;
+  if (id >= n_prefix) {   // workgroup-uniform
+    id -= n_prefix;
+    const int sp = id % p.nss;
+    id /= p.nss;
+    shared_suffix_body<T>(p, reinterpret_cast<float*>(lds), id / p.H, id % p.H, sp);
+    return;
+  }
+  const int range = id % p.nsp;
+  id /= p.nsp;
+  const int qt = id % p.qtiles;
+  id /= p.qtiles;
+  const int h = id % p.H, g = id / p.H;
+  const int k0 = range * p.kps, k1 = min(p.P, k0 + p.kps);   // k1 > k0 by the plan
+  const int nt = (k1 - k0 + 31) >> 5;                        // 32-key tiles of the range; wave w walks tiles w, w + 4, ...
+  const int iters = (nt + 3) >> 2;
+  const int r = qt * 32 + li;                                // this lane's query: row r of the group
+  const bool qlive = r < p.R;
+
+  // ---- Q fragments (B operand of S^T): lane holds Q[r][ks*16 + lh*8 .. +8]; padding rows hold zeros and write nothing ----
+  i32x4 qf[8];
+  {
+    const char* qp = p.q + ((int64_t)(g * p.R + (qlive ? r : 0)) * p.q_bs + (int64_t)h * kDecD + lh * 8) * 2;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      const i32x4 z = {0, 0, 0, 0};
+      qf[ks] = qlive ? *reinterpret_cast<const i32x4*>(qp + ks * 32) : z;
+    }
+  }
+  f32x16 o[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[i][e] = 0.0f;
+  float m_run = kNeg, l_run = 0.0f;
+
+  // lane (li, lh) owns key row kv0 + li of a tile: its 16-byte chunks c*16 + lh*8 (c = 0..7) are the K fragments of the S^T chain (A operand, k-step c)
+  // and the V chunks 2c + lh of the transposed LDS store.  A row at or behind k1 (= P in the last tile of the last range) is NOT loaded.
+  const char* kbase = p.kp + ((int64_t)g * p.kp_bs + (int64_t)h * kDecD + lh * 8) * 2;
+  const char* vbase = p.vp + ((int64_t)g * p.vp_bs + (int64_t)h * kDecD + lh * 8) * 2;
+  char* v_lds = lds + wave * (kDecD * kShVPitch);
+  i32x4 kreg[8], vreg[8];
+  auto load_tile = [&](int kv0) {
+    const int kv = kv0 + li;
+    const bool ok = kv < k1;
+    const char* kr = kbase + (int64_t)kv * p.kp_rs * 2;
+    const char* vr = vbase + (int64_t)kv * p.vp_rs * 2;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const i32x4 z = {0, 0, 0, 0};
+      kreg[c] = ok ? *reinterpret_cast<const i32x4*>(kr + c * 32) : z;
+      vreg[c] = ok ? *reinterpret_cast<const i32x4*>(vr + c * 32) : z;
+    }
+  };
+  int t = wave;
+  if (t < nt) load_tile(k0 + t * 32);
+  for (int it = 0; it < iters; ++it, t += 4) {
+    const bool act = t < nt;            // wave-uniform; every wave keeps the barriers of all `iters` rounds
+    const int kv0 = k0 + t * 32;
+    __syncthreads();                    // the wave's previous V^T tile is consumed
+    f32x16 s;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) s[e] = 0.0f;
+    if (act) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int cc = 2 * c + lh;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const uint32_t w = (uint32_t)vreg[c][e];
+          *reinterpret_cast<uint16_t*>(v_lds + (cc * 8 + 2 * e) * kShVPitch + li * 2) = (uint16_t)(w & 0xffff);
+          *reinterpret_cast<uint16_t*>(v_lds + (cc * 8 + 2 * e + 1) * kShVPitch + li * 2) = (uint16_t)(w >> 16);
+        }
+      }
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) s = Elem<T>::mfma(kreg[ks], qf[ks], s);   // S^T[key][query]
+    }
+    if (t + 4 < nt) load_tile(k0 + (t + 4) * 32);   // in flight under the softmax and the P V chain
+    __syncthreads();
+    if (!act) continue;
+    if (kv0 + 32 > k1) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int kv = kv0 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+        s[e] = kv >= k1 ? kNeg : s[e];
+      }
+    }
+    float mx = s[0];
+#pragma unroll
+    for (int e = 1; e < 16; ++e) mx = fmaxf(mx, s[e]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);
+    const float mc = m_new * p.scale_log2;
+    float rs = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const float pv = __builtin_amdgcn_exp2f(fmaf(s[e], p.scale_log2, -mc));   // masked: exp2(-huge) == 0
+      s[e] = pv;
+      rs += pv;
+    }
+    rs += __shfl_xor(rs, 32, 64);
+    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2);
+    l_run = fmaf(l_run, alpha, rs);
+    m_run = m_new;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) o[i][e] *= alpha;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      i32x4 pf;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pf[e] = (int)(Elem<T>::pack2(s[a * 8 + 2 * e], s[a * 8 + 2 * e + 1]));
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const char* vp = v_lds + (i * 32 + li) * kShVPitch + (16 * a + 4 * lh) * 2;
+        const i32x2 lo = *reinterpret_cast<const i32x2*>(vp);
+        const i32x2 hi = *reinterpret_cast<const i32x2*>(vp + 16);
+        const i32x4 vf = {lo[0], lo[1], hi[0], hi[1]};
+        o[i] = Elem<T>::mfma(vf, pf, o[i]);
+      }
+    }
+  }
+
+  // ---- the four wave states -> one: 0 <- 2 and 1 <- 3, then 0 <- 1, through two slots of [66][64] floats (lane-major: every lane reads back what the same
+  // lane of the other wave wrote).  A fixed order; a wave that walked no tile holds the empty state (m = kNeg, l = 0, O = 0) and weighs exp2(-huge) = 0 ----
+  float* st = reinterpret_cast<float*>(lds);
+  auto put = [&](int slot) {
+    float* d = st + slot * (66 * 64) + lane;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) d[(i * 16 + e) * 64] = o[i][e];
+    d[64 * 64] = m_run;
+    d[65 * 64] = l_run;
+  };
+  auto take = [&](int slot) {
+    const float* d = st + slot * (66 * 64) + lane;
+    const float mb = d[64 * 64], lb = d[65 * 64];
+    const float mn = fmaxf(m_run, mb);
+    const float fa = __builtin_amdgcn_exp2f((m_run - mn) * p.scale_log2), fb = __builtin_amdgcn_exp2f((mb - mn) * p.scale_log2);
+    l_run = fmaf(l_run, fa, lb * fb);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) o[i][e] = fmaf(o[i][e], fa, d[(i * 16 + e) * 64] * fb);
+    m_run = mn;
+  };
+  __syncthreads();
+  if (wave >= 2) put(wave - 2);
+  __syncthreads();
+  if (wave < 2) take(wave);
+  __syncthreads();
+  if (wave == 1) put(0);
+  __syncthreads();
+  if (wave != 0) return;
+  take(0);
+  if (!qlive) return;   // padding query rows write no record
+  float* rec = p.ws_p + ((((int64_t)g * p.H + h) * p.R + r) * p.nsp + range) * kSplRec;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      const f32x4 ov = {o[i][4 * gq + 0], o[i][4 * gq + 1], o[i][4 * gq + 2], o[i][4 * gq + 3]};
+      *reinterpret_cast<f32x4*>(rec + i * 32 + 8 * gq + 4 * lh) = ov;
+    }
+  if (lh == 0) { rec[128] = m_run * p.scale_log2; rec[129] = l_run; }
+}
+
+// one workgroup (one wave) per query row (b, i, h): n_p prefix records of its group row, then n_s suffix records of its own row, ascending
+template <typename T>
+__global__ __launch_bounds__(64) void attn_shared_merge_kernel(const SharedParams p, int n_p, int n_s) {
+  const int lane = threadIdx.x, i = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int g = b / p.R, rr = b - g * p.R;
+  const float* ra = p.ws_p + ((((int64_t)g * p.H + h) * ((int64_t)p.R * p.Sq) + (int64_t)rr * p.Sq + i) * n_p) * kSplRec;
+  const float* rb = p.ws_s + ((((int64_t)b * p.H + h) * p.Sq + i) * n_s) * kSplRec;
+  float mm = kNeg * 2.0f;
+  for (int s = 0; s < n_p; ++s) mm = fmaxf(mm, ra[s * kSplRec + 128] * p.m_mult);
+  for (int s = 0; s < n_s; ++s) mm = fmaxf(mm, rb[s * kSplRec + 128] * p.m_mult);
+  float ll = 0.0f, a0 = 0.0f, a1 = 0.0f;
+  for (int s = 0; s < n_p; ++s) {
+    const float f = __builtin_amdgcn_exp2f(ra[s * kSplRec + 128] * p.m_mult - mm);   // empty records: exp2(-huge) == 0
+    ll = fmaf(ra[s * kSplRec + 129], f, ll);
+    a0 = fmaf(ra[s * kSplRec + 2 * lane], f, a0);
+    a1 = fmaf(ra[s * kSplRec + 2 * lane + 1], f, a1);
+  }
+  for (int s = 0; s < n_s; ++s) {
+    const float f = __builtin_amdgcn_exp2f(rb[s * kSplRec + 128] * p.m_mult - mm);
+    ll = fmaf(rb[s * kSplRec + 129], f, ll);
+    a0 = fmaf(rb[s * kSplRec + 2 * lane], f, a0);
+    a1 = fmaf(rb[s * kSplRec + 2 * lane + 1], f, a1);
+  }
+  const float inv = 1.0f / ll;
+  uint32_t* op = reinterpret_cast<uint32_t*>(p.o + ((int64_t)b * p.o_bs + (int64_t)i * p.o_rs + (int64_t)h * kDecD + 2 * lane) * 2);
+  *op = Elem<T>::pack2(a0 * inv, a1 * inv);
+}
+
+// fp32 (the verify mode): one workgroup per (b, i, h); wave w takes keys w, w + 4, ... of the row's P + n_s keys (prefix first), lane l the dims 2l, 2l + 1
+__global__ __launch_bounds__(256) void attn_shared_f32_kernel(const SharedParams p) {
+  __shared__ float part[4][kSplRec];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int g = b / p.R;
+  int ns = p.sfx_len ? min(p.sfx_len[b], p.max_sfx) : p.max_sfx;
+  if (p.causal) ns = min(ns, p.sfx_q_off + i + 1);
+  if (ns < 0) ns = 0;
+  const f32x2 qv = *reinterpret_cast<const f32x2*>(reinterpret_cast<const float*>(p.q) + (int64_t)b * p.q_bs + (int64_t)i * p.q_rs + (int64_t)h * kDecD + 2 * lane);
+  const float q0 = qv[0] * p.scale_log2, q1 = qv[1] * p.scale_log2;
+  const float* kpf = reinterpret_cast<const float*>(p.kp) + (int64_t)g * p.kp_bs + (int64_t)h * kDecD + 2 * lane;
+  const float* vpf = reinterpret_cast<const float*>(p.vp) + (int64_t)g * p.vp_bs + (int64_t)h * kDecD + 2 * lane;
+  const float* ksf = reinterpret_cast<const float*>(p.ks) + (int64_t)b * p.ks_bs + (int64_t)h * kDecD + 2 * lane;
+  const float* vsf = reinterpret_cast<const float*>(p.vs) + (int64_t)b * p.vs_bs + (int64_t)h * kDecD + 2 * lane;
+  float m = kNeg, l = 0.0f, o0 = 0.0f, o1 = 0.0f;
+  const int total = p.P + ns;
+  for (int j = wave; j < total; j += 4) {
+    const bool pre = j < p.P;
+    const f32x2 kk = *reinterpret_cast<const f32x2*>(pre ? kpf + (int64_t)j * p.kp_rs : ksf + (int64_t)(j - p.P) * p.ks_rs);
+    const f32x2 vv = *reinterpret_cast<const f32x2*>(pre ? vpf + (int64_t)j * p.vp_rs : vsf + (int64_t)(j - p.P) * p.vs_rs);
+    const float s = wave_sum(fmaf(q0, kk[0], q1 * kk[1]));
+    const float mn = fmaxf(m, s);
+    const float alpha = __builtin_amdgcn_exp2f(m - mn), pr = __builtin_amdgcn_exp2f(s - mn);
+    l = fmaf(l, alpha, pr);
+    o0 = fmaf(o0, alpha, pr * vv[0]);
+    o1 = fmaf(o1, alpha, pr * vv[1]);
+    m = mn;
+  }
+  if (lane == 0) { part[wave][128] = m; part[wave][129] = l; }
+  part[wave][2 * lane] = o0;
+  part[wave][2 * lane + 1] = o1;
+  __syncthreads();
+  if (wave == 0) {
+    const float mm = fmaxf(fmaxf(part[0][128], part[1][128]), fmaxf(part[2][128], part[3][128]));
+    float ll = 0.0f, a0 = 0.0f, a1 = 0.0f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float f = __builtin_amdgcn_exp2f(part[w][128] - mm);
+      ll = fmaf(part[w][129], f, ll);
+      a0 = fmaf(part[w][2 * lane], f, a0);
+      a1 = fmaf(part[w][2 * lane + 1], f, a1);
+    }
+    const f32x2 r = {a0 / ll, a1 / ll};
+    *reinterpret_cast<f32x2*>(reinterpret_cast<float*>(p.o) + (int64_t)b * p.o_bs + (int64_t)i * p.o_rs + (int64_t)h * kDecD + 2 * lane) = r;
+  }
+}
+
+template <typename T, int NW, bool LIVE>
+void launch_shared_pass_nw(const AttnParams& a, const KsplitPlan& pl, hipStream_t stream) {
+  hipLaunchKernelGGL((attn_mfma_kernel<T, 128, NW, true, LIVE>), dim3(pl.chunks * pl.nsplit, a.H, a.B), dim3(64 * NW), 0, stream, a);
+}
+template <typename T, bool LIVE>
+void launch_shared_pass(AttnParams a, const KsplitPlan& pl, hipStream_t stream) {
+  a.nsplit = pl.nsplit;
+  a.kps = pl.kps;
+  switch (pl.nw) {
+    case 1: launch_shared_pass_nw<T, 1, LIVE>(a, pl, stream); break;
+    case 2: launch_shared_pass_nw<T, 2, LIVE>(a, pl, stream); break;
+    case 3: launch_shared_pass_nw<T, 3, LIVE>(a, pl, stream); break;
+    default: launch_shared_pass_nw<T, 4, LIVE>(a, pl, stream); break;
+  }
+}
+
+template <typename T>
+int launch_shared(SharedParams p, float scale, float* ws, hipStream_t stream) {
+  if (p.Sq == 1) {
+    const SharedPlan pl = shared_plan(p.G, p.H, p.R, p.P, p.max_sfx);
+    p.nsp = pl.nsp; p.kps = pl.kps; p.qtiles = pl.qtiles; p.nss = pl.nss; p.kps_s = pl.kps_s;
+    p.ws_p = ws;
+    p.ws_s = ws + (int64_t)p.B * p.H * pl.nsp * kSplRec;
+    p.m_mult = 1.0f;
+    const int64_t wgs = (int64_t)p.G * p.H * pl.qtiles * pl.nsp + (int64_t)p.B * p.H * pl.nss;
+    hipLaunchKernelGGL(attn_shared_decode_kernel<T>, dim3((unsigned)wgs), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(attn_shared_merge_kernel<T>, dim3(1, p.H, p.B), dim3(64), 0, stream, p, pl.nsp, pl.nss);
+    STLLM_CHECK_LAUNCH("stllm_attention_shared(decode)");
+    stllm_set_last_kernel("attn_shared_decode_kernel");
+    return STLLM_OK;
+  }
+  const KsplitPlan pa = ksplit_plan(p.G, p.H, p.R * p.Sq, p.P), pb = ksplit_plan(p.B, p.H, p.Sq, p.max_sfx);
+  p.ws_p = ws;
+  p.ws_s = ws + (int64_t)p.B * p.H * p.Sq * pa.nsplit * kSplRec;
+  p.m_mult = p.scale_log2;
+  AttnParams a{};
+  a.q = p.q; a.q_bs = (int64_t)p.R * p.q_bs; a.q_rs = p.q_rs;       // the R * Sq query rows of a group at ONE row stride (checked by the caller)
+  a.k = p.kp; a.k_bs = p.kp_bs; a.k_rs = p.kp_rs;
+  a.v = p.vp; a.v_bs = p.vp_bs; a.v_rs = p.vp_rs;
+  a.B = p.G; a.H = p.H; a.Sq = p.R * p.Sq; a.Skv = p.P; a.D = kDecD;
+  a.scale = scale; a.scale_log2 = p.scale_log2;
+  a.ws = p.ws_p;
+  launch_shared_pass<T, false>(a, pa, stream);
+  AttnParams s{};
+  s.q = p.q; s.q_bs = p.q_bs; s.q_rs = p.q_rs;
+  s.k = p.ks; s.k_bs = p.ks_bs; s.k_rs = p.ks_rs;
+  s.v = p.vs; s.v_bs = p.vs_bs; s.v_rs = p.vs_rs;
+  s.B = p.B; s.H = p.H; s.Sq = p.Sq; s.Skv = p.max_sfx; s.D = kDecD;
+  s.scale = scale; s.scale_log2 = p.scale_log2;
+  s.causal = p.causal; s.q_off = p.causal ? p.sfx_q_off : 0;
+  s.kv_len = p.sfx_len;
+  s.ws = p.ws_s;
+  launch_shared_pass<T, true>(s, pb, stream);
+  hipLaunchKernelGGL(attn_shared_merge_kernel<T>, dim3(p.Sq, p.H, p.B), dim3(64), 0, stream, p, pa.nsplit, pb.nsplit);
+  STLLM_CHECK_LAUNCH("stllm_attention_shared(extend)");
+  stllm_set_last_kernel("attn_shared_extend");
+  return STLLM_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t stllm_attention_shared_workspace_bytes(int B, int G, int H, int Sq, int P, int max_sfx) {
+  if (B <= 0 || G <= 0 || B % G != 0 || H <= 0 || Sq <= 0 || P <= 0 || max_sfx <= 0) return -1;
+  const int R = B / G;
+  if (Sq == 1) {
+    const SharedPlan pl = shared_plan(G, H, R, P, max_sfx);
+    return (int64_t)B * H * (pl.nsp + pl.nss) * kSplRec * 4;
+  }
+  return (int64_t)B * H * Sq * (ksplit_plan(G, H, R * Sq, P).nsplit + ksplit_plan(B, H, Sq, max_sfx).nsplit) * kSplRec * 4;
+}
+
+extern "C" int stllm_attention_shared(int dtype, const void* q, int64_t q_bs, int64_t q_rs, const void* kp, int64_t kp_bs, int64_t kp_rs,
+                                      const void* vp, int64_t vp_bs, int64_t vp_rs, int P, const void* ks, int64_t ks_bs, int64_t ks_rs,
+                                      const void* vs, int64_t vs_bs, int64_t vs_rs, const int32_t* sfx_len, int max_sfx, int sfx_q_off,
+                                      void* out, int64_t o_bs, int64_t o_rs, int B, int G, int H, int Sq, int D, float scale, int causal,
+                                      void* workspace, int64_t workspace_bytes, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  STLLM_CHECK_ARG(q && kp && vp && ks && vs && out, "stllm_attention_shared: null pointer");
+  STLLM_CHECK_ARG(B > 0 && G > 0 && B % G == 0 && H > 0 && Sq > 0 && P > 0 && max_sfx > 0 && sfx_q_off >= 0,
+                  "stllm_attention_shared: needs B %% G == 0 and a non-empty prefix and suffix (B %d, G %d, H %d, Sq %d, P %d, max_sfx %d, sfx_q_off %d)", B, G, H, Sq, P, max_sfx, sfx_q_off);
+  if (D != kDecD || (dtype != STLLM_BF16 && dtype != STLLM_F16 && dtype != STLLM_F32)) {
+    stllm_set_error("stllm_attention_shared: head_dim %d / dtype %d unsupported (bf16 / fp16 / fp32 at head_dim 128)", D, dtype);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  STLLM_CHECK_ARG(aligned16(q) && aligned16(kp) && aligned16(vp) && aligned16(ks) && aligned16(vs) && aligned16(out) && ((uintptr_t)sfx_len & 3) == 0,
+                  "stllm_attention_shared: pointers must be 16-byte aligned");
+  STLLM_CHECK_ARG(q_bs % 8 == 0 && q_rs % 8 == 0 && kp_bs % 8 == 0 && kp_rs % 8 == 0 && vp_bs % 8 == 0 && vp_rs % 8 == 0 && ks_bs % 8 == 0 && ks_rs % 8 == 0 &&
+                      vs_bs % 8 == 0 && vs_rs % 8 == 0 && o_bs % 8 == 0 && o_rs % 8 == 0, "stllm_attention_shared: strides must be multiples of 8 elements");
+  SharedParams p{};
+  p.q = (const char*)q; p.q_bs = q_bs; p.q_rs = q_rs;
+  p.kp = (const char*)kp; p.kp_bs = kp_bs; p.kp_rs = kp_rs;
+  p.vp = (const char*)vp; p.vp_bs = vp_bs; p.vp_rs = vp_rs;
+  p.ks = (const char*)ks; p.ks_bs = ks_bs; p.ks_rs = ks_rs;
+  p.vs = (const char*)vs; p.vs_bs = vs_bs; p.vs_rs = vs_rs;
+  p.o = (char*)out; p.o_bs = o_bs; p.o_rs = o_rs;
+  p.sfx_len = sfx_len; p.max_sfx = max_sfx; p.sfx_q_off = sfx_q_off;
+  p.B = B; p.G = G; p.R = B / G; p.H = H; p.Sq = Sq; p.P = P;
+  p.scale_log2 = scale * 1.44269504088896340736f;
+  p.causal = causal;
+  if (dtype == STLLM_F32) {
+    hipLaunchKernelGGL(attn_shared_f32_kernel, dim3(Sq, H, B), dim3(256), 0, stream, p);
+    STLLM_CHECK_LAUNCH("stllm_attention_shared(fp32)");
+    stllm_set_last_kernel("attn_shared_f32_kernel");
+    return STLLM_OK;
+  }
+  if (Sq > 1 && p.R > 1 && q_bs != (int64_t)Sq * q_rs) {
+    stllm_set_error("stllm_attention_shared: Sq > 1 in bf16 / fp16 needs the query rows of a group at one row stride (q_bs == Sq * q_rs; got %lld, %d x %lld)",
+                    (long long)q_bs, Sq, (long long)q_rs);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  STLLM_CHECK_ARG(workspace && aligned16(workspace) && workspace_bytes >= stllm_attention_shared_workspace_bytes(B, G, H, Sq, P, max_sfx),
+                  "stllm_attention_shared: workspace too small or misaligned");
+  float* ws = reinterpret_cast<float*>(workspace);
+  return dtype == STLLM_BF16 ? launch_shared<bf16_t>(p, scale, ws, stream) : launch_shared<f16_t>(p, scale, ws, stream);
 }
 
 #ifdef STLLM_ATTN_TRACE

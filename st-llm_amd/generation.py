@@ -99,9 +99,11 @@ def _ends_in_stop(ids, stop_sequences):
 class _CacheStepper:
     """next-token logits from the model: prefill once, then one decode step per token; rows can be re-ordered (beams)."""
 
-    def __init__(self, lm_wrapper, inputs_embeds, rows, max_new_tokens, use_cache=True, prefix=None, lengths=None):
+    def __init__(self, lm_wrapper, inputs_embeds, rows, max_new_tokens, use_cache=True, prefix=None, lengths=None, share_prefix=False):
         self.m, self.lm = lm_wrapper, lm_wrapper.model
         self.use_cache = use_cache
+        if share_prefix and not use_cache:
+            raise ValueError("generate(share_prefix=True) needs use_cache: what is shared is the KV cache of the prompt's first positions")
         emb = inputs_embeds.float()
         B, S, _ = emb.shape
         self.rep = rows // B                      # beams per prompt
@@ -115,7 +117,8 @@ class _CacheStepper:
             if prefix is not None:
                 if prefix.batch not in (1, B):
                     raise ValueError("generate(prefix=..., lengths=...): the prefix holds one row shared by every prompt, or one row per prompt")
-                self.cache = prefix.fork(rows=B, max_len=prefix.len + S + max_new_tokens)
+                # share_prefix: the rows READ the prefix where it is (KVCache.share) instead of owning a copy of it each
+                self.cache = prefix.share(rows=B, max_new=S + max_new_tokens) if share_prefix else prefix.fork(rows=B, max_len=prefix.len + S + max_new_tokens)
                 _, h16 = self.lm.extend(emb, self.cache, lengths=lengths)
             else:
                 self.cache = self.lm.new_cache(B, S + max_new_tokens, emb.device)
@@ -124,7 +127,9 @@ class _CacheStepper:
             last = h16.view(B, S, -1)[torch.arange(B), torch.tensor(lengths) - 1].contiguous()
             logits = self.m.logits_from(last, B, 1)[:, 0]
             if self.rep > 1:
-                self.cache = self.cache.fork(rows=rows)
+                if share_prefix and self.cache.base is None:
+                    raise NotImplementedError("generate(share_prefix=True, lengths=...) with beams needs prefix=: a ragged prompt cache cannot be a shared base")
+                self.cache = self.cache.share(rows=rows) if share_prefix else self.cache.fork(rows=rows)   # share: the same base, the question rows copied per beam
                 logits = logits.repeat_interleave(self.rep, dim=0)
             self.logits = logits.float()
         elif prefix is not None:
@@ -132,18 +137,21 @@ class _CacheStepper:
             # — a copy of the prefix rows, made once per beam —, so the prefix itself stays as it was and serves the next call.
             if not use_cache or prefix.batch != B:
                 raise ValueError("generate(prefix=...): needs use_cache and one prefix row per prompt")
-            self.cache = prefix.fork(max_len=prefix.len + S + max_new_tokens)
+            self.cache = prefix.share(max_new=S + max_new_tokens) if share_prefix else prefix.fork(max_len=prefix.len + S + max_new_tokens)
             _, h16 = self.lm.extend(emb, self.cache)
             logits = self.m.logits_from(h16.view(B, S, -1)[:, -1].contiguous(), B, 1)[:, 0]
             if self.rep > 1:
-                self.cache = self.cache.fork(rows=rows)
+                self.cache = self.cache.share(rows=rows) if share_prefix else self.cache.fork(rows=rows)
                 logits = logits.repeat_interleave(self.rep, dim=0)
             self.logits = logits.float()
         elif use_cache:
             self.cache = self.lm.new_cache(B, S + max_new_tokens, emb.device)
             _, h16 = self.lm.prefill(emb, None, cache=self.cache)
             logits = self.m.logits_from(h16.view(B, S, -1)[:, -1].contiguous(), B, 1)[:, 0]
-            if self.rep > 1:                      # replicate the prompt's cache rows to the beams
+            if self.rep > 1 and share_prefix:     # the prompt's cache is the base of its beams: never replicated, read once per step for all of them
+                self.cache = self.cache.share(rows=rows, max_new=max_new_tokens)
+                logits = logits.repeat_interleave(self.rep, dim=0)
+            elif self.rep > 1:                    # replicate the prompt's cache rows to the beams
                 big = self.lm.new_cache(rows, S + max_new_tokens, emb.device)
                 for dst, src in zip(big.qkv, self.cache.qkv):
                     dst[:, :S] = src[:, :S].repeat_interleave(self.rep, dim=0)
@@ -160,7 +168,7 @@ class _CacheStepper:
         tok = self.lm.embed_tokens(next_tokens.view(-1, 1).cpu())
         if self.use_cache:
             if beam_idx is not None and not torch.equal(beam_idx.cpu(), torch.arange(beam_idx.numel())):
-                n = self.cache.len
+                n = self.cache.len - self.cache.base_len   # a shared base is common to the beams of a prompt: only the positions behind it move
                 idx = beam_idx.to(self.cache.qkv[0].device)
                 for buf in self.cache.qkv:        # _reorder_cache: past.index_select(0, beam_idx), only the rows in use
                     buf[:, :n] = buf[:, :n].index_select(0, idx)
@@ -178,19 +186,23 @@ class _CacheStepper:
 @torch.no_grad()
 def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sample=False, min_length=0, top_p=1.0,
              temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, stopping_criteria=None, eos_token_id=2,
-             pad_token_id=0, use_cache=True, generator=None, prefix=None, lengths=None, stop_sequences=None, return_lengths=False):
+             pad_token_id=0, use_cache=True, generator=None, prefix=None, lengths=None, stop_sequences=None, return_lengths=False,
+             share_prefix=False):
     """Returns the generated ids [B, n] (the prompt has no ids), HF semantics as described in the module docstring.
     prefix: a KVCache that already holds the first positions of every prompt (LlamaModel.prefill(cache=...) / Chat.prefill_video); `inputs_embeds` is then
     the remainder of the prompt, appended behind it in one pass (LlamaModel.extend).  The prefix is left unchanged.
     lengths: per-row token counts of a right-padded `inputs_embeds` (a ragged batch in one call; with a prefix the prefix may hold one shared row).
     stop_sequences: list of 1-D id tensors — a row whose generated ids end in one of them is finished from that step on and emits pad_token_id, like a
     row that emitted EOS (beam search: the prompt is closed when its first beam ends in one, its open beams become hypotheses).
-    return_lengths: also return the number of generated tokens per row (the rest of the row is padding)."""
+    return_lengths: also return the number of generated tokens per row (the rest of the row is padding).
+    share_prefix: the rows that have the same first positions — the questions behind one prefix row, the beams of a prompt — read ONE physical copy of them
+    (KVCache.share, hip.attention_shared) instead of owning a copy each; the beam re-ordering then moves the positions behind it only.
+    Same ids up to the summation order of the attention; needs use_cache.  False (default): every row owns its copy, as always."""
     B = inputs_embeds.shape[0]
     dev = inputs_embeds.device
     stop_sequences = list(stop_sequences) if stop_sequences else None
     if num_beams == 1:
-        st = _CacheStepper(lm_wrapper, inputs_embeds, B, max_new_tokens, use_cache, prefix, lengths)
+        st = _CacheStepper(lm_wrapper, inputs_embeds, B, max_new_tokens, use_cache, prefix, lengths, share_prefix)
         ids = torch.zeros((B, 0), dtype=torch.long, device=dev)
         unfinished = torch.ones(B, dtype=torch.long, device=dev)
         n_gen = torch.zeros(B, dtype=torch.long, device=dev)
@@ -218,7 +230,7 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
     if do_sample:
         raise NotImplementedError("beam-sample is not used by the reference (demo: num_beams=5, do_sample=False)")
     nb = num_beams
-    st = _CacheStepper(lm_wrapper, inputs_embeds, B * nb, max_new_tokens, use_cache, prefix, lengths)
+    st = _CacheStepper(lm_wrapper, inputs_embeds, B * nb, max_new_tokens, use_cache, prefix, lengths, share_prefix)
     ids = torch.zeros((B * nb, 0), dtype=torch.long, device=dev)
     beam_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
     beam_scores[:, 1:] = -1e9

@@ -28,7 +28,8 @@ EXPORTS = ["stllm_last_error", "stllm_abi_version", "stllm_last_kernel", "stllm_
            "stllm_qformer_layers_scratch_bytes", "stllm_qformer_layers", "stllm_split3_rows", "stllm_gemm_split_ws_bytes",
            "stllm_lora_down_workspace_bytes", "stllm_lora_down", "stllm_llama_layers_lora_scratch_bytes", "stllm_llama_layers_lora",
            "stllm_attention_offset_workspace_bytes", "stllm_attention_offset", "stllm_llama_layers_extend", "stllm_gemv_w8",
-           "stllm_attention_decode_ragged_workspace_bytes", "stllm_attention_decode_ragged", "stllm_kv_append_rows"]
+           "stllm_attention_decode_ragged_workspace_bytes", "stllm_attention_decode_ragged", "stllm_kv_append_rows",
+           "stllm_attention_shared_workspace_bytes", "stllm_attention_shared"]
 
 
 def torch_dtype(d):
@@ -158,6 +159,9 @@ def _bind(L, strict=True):
     B("stllm_attention_decode_ragged", [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int,
                                         c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_int64, c_void_p])
     B("stllm_kv_append_rows", [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
+    B("stllm_attention_shared_workspace_bytes", [c_int] * 6, c_int64)
+    B("stllm_attention_shared", [c_int] + [c_void_p, c_int64, c_int64] * 3 + [c_int] + [c_void_p, c_int64, c_int64] * 2 + [c_void_p, c_int, c_int] +
+      [c_void_p, c_int64, c_int64] + [c_int] * 5 + [c_float, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_gemm_profile", [c_int, c_char_p])
     B("stllm_gemm_profile_count", [])
     B("stllm_gemm_profile_read", [c_int, c_char_p, c_int, ctypes.POINTER(c_float), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int)])
@@ -983,6 +987,34 @@ def attention_decode_ragged(q, k, v, kv_len, *, B, H, max_kv, D, scale, out=None
     _check(lib().stllm_attention_decode_ragged(dtype_code(td), _p(q), q.stride(0) if q_stride is None else q_stride, _p(k), ks[0], ks[1], _p(v), vs[0], vs[1],
                                                _p(out), out.stride(0), B, H, _p(kv_len), max_kv, D, scale, _p(ws), need, _stream()),
            "stllm_attention_decode_ragged")
+    return out
+
+
+def attention_shared(q, kp, vp, ks, vs, *, B, G, H, Sq, P, D, scale, max_sfx, sfx_len=None, sfx_q_off=0, causal=False, out=None,
+                     q_strides=None, kp_strides=None, ks_strides=None):
+    """stllm_attention_shared: B = G * R query rows, the R rows of group g read the P keys of prefix row g ONCE (kp / vp: 2-D views of the prefix buffer,
+    (batch, row) strides kp_strides, never written) and each row b its own suffix keys [0, min(sfx_len[b], max_sfx)) (ks / vs, strides ks_strides);
+    with `causal` suffix key j is visible to query row i iff j <= sfx_q_off + i.  sfx_len: int32 [B] on the device or None (max_sfx keys in every row).
+    q: 2-D view, (batch, row) strides q_strides (default: Sq consecutive rows per batch entry).  bf16 / fp16 / fp32 at D = 128; anything else is an
+    error (STLLM_ERR_UNSUPPORTED), not a fallback.  The partial-state workspace comes from the per-(device, stream) scratch cache (split_workspace)."""
+    td = q.dtype
+    if sfx_len is not None:
+        _req(sfx_len, torch.int32, "sfx_len")
+        if sfx_len.numel() != B:
+            raise RuntimeError(f"attention_shared: sfx_len has {sfx_len.numel()} entries for B = {B}")
+    qs = q_strides if q_strides is not None else (Sq * q.stride(0), q.stride(0))
+    kps = kp_strides if kp_strides is not None else (P * kp.stride(0), kp.stride(0))
+    kss = ks_strides if ks_strides is not None else (max_sfx * ks.stride(0), ks.stride(0))
+    if out is None:
+        out = torch.empty((B * Sq, H * D), device=q.device, dtype=td)
+    need = int(lib().stllm_attention_shared_workspace_bytes(B, G, H, Sq, P, max_sfx))
+    if need < 0:
+        raise RuntimeError(f"stllm_attention_shared_workspace_bytes: bad shape (B={B}, G={G}, H={H}, Sq={Sq}, P={P}, max_sfx={max_sfx})")
+    ws = split_workspace(q.device, need) if td != torch.float32 else None
+    _check(lib().stllm_attention_shared(dtype_code(td), _p(q), qs[0], qs[1], _p(kp), kps[0], kps[1], _p(vp), kps[0], kps[1], P,
+                                        _p(ks), kss[0], kss[1], _p(vs), kss[0], kss[1], _p(sfx_len), max_sfx, int(sfx_q_off),
+                                        _p(out), Sq * out.stride(0), out.stride(0), B, G, H, Sq, D, scale, int(causal),
+                                        _p(ws), ws.numel() if ws is not None else 0, _stream()), "stllm_attention_shared")
     return out
 
 

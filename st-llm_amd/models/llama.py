@@ -108,12 +108,17 @@ class KVCache:
     are untouched.  Otherwise the cache is RAGGED: `lens` is a host list of `batch` ints, row b holds positions [0, lens[b]) and `len` == max(lens), so
     bounds checks against `len` keep their meaning.  prefill() with a right-padded mask and extend(lengths=) make a cache ragged; decode_step then appends
     token b at position lens[b] (RoPE at that position) and row b attends its own lens[b] + 1 keys.  Rows behind lens[b] hold don't-care
-    values that later steps overwrite."""
+    values that later steps overwrite.
+    `base` is None for the cache described so far.  share() makes a cache with a BASE: the first base_len = P positions of every row live
+    in another cache, held by reference and never written — row b reads base row b // (batch // base.batch), so the rows come in contiguous groups that
+    share one physical prefix — and `qkv` holds the positions >= P only, [batch, max_len - P, 3 * hidden], local index = position - P.  `len`, `lens` and
+    `max_len` keep counting TOTAL positions (RoPE positions, bounds checks).  One level only: the base has no base."""
 
-    def __init__(self, n_layers, batch, max_len, hidden, dtype, device):
+    def __init__(self, n_layers, batch, max_len, hidden, dtype, device, base=None):
         self.max_len, self.batch, self.hidden = max_len, batch, hidden
-        self.qkv = [torch.empty((batch, max_len, 3 * hidden), device=device, dtype=dtype) for _ in range(n_layers)]
-        self.len = 0
+        self.base, self.base_len = base, (base.len if base is not None else 0)
+        self.qkv = [torch.empty((batch, max_len - self.base_len, 3 * hidden), device=device, dtype=dtype) for _ in range(n_layers)]
+        self.len = self.base_len
         self.lens = None
 
     def set_lens(self, lens):
@@ -135,16 +140,48 @@ class KVCache:
         assert rows % self.batch == 0 and max_len >= self.len
         new = KVCache(len(self.qkv), rows, max_len, self.hidden, self.qkv[0].dtype, self.qkv[0].device)
         n, rep = self.len, rows // self.batch
-        for dst, src in zip(new.qkv, self.qkv):
-            dst[:, :n] = src[:, :n].repeat_interleave(rep, dim=0) if rep > 1 else src[:, :n]
+        if self.base is not None:   # a cache with a base materialises: a dense private copy of base rows + suffix rows (for paths that do not share)
+            P, grp = self.base_len, rows // self.base.batch
+            for dst, pre, src in zip(new.qkv, self.base.qkv, self.qkv):
+                dst[:, :P] = pre[:, :P].repeat_interleave(grp, dim=0) if grp > 1 else pre[:, :P]
+                dst[:, P:n] = src[:, :n - P].repeat_interleave(rep, dim=0) if rep > 1 else src[:, :n - P]
+        else:
+            for dst, src in zip(new.qkv, self.qkv):
+                dst[:, :n] = src[:, :n].repeat_interleave(rep, dim=0) if rep > 1 else src[:, :n]
         new.len = n
         if self.lens is not None:   # ragged: every copy of a row inherits its length
             new.lens = [l for l in self.lens for _ in range(rep)]
         return new
 
+    def share(self, rows=None, max_new=None):
+        """a new cache whose first positions are THIS cache, by reference: nothing is copied, this cache is never written through it, and the decode
+        attention reads its K / V once per group of rows instead of once per row (hip.attention_shared).  Every row of this cache serves
+        rows // batch consecutive rows of the new one; max_new positions can be appended behind it.  Needs a uniform cache (lens is None).
+        On a cache that already has a base (the beams of a ragged batch): the SAME base, and copies of the suffix rows, repeated like fork(rows=);
+        max_new defaults to this cache's own room."""
+        rows = self.batch if rows is None else rows
+        assert rows % self.batch == 0
+        if self.base is not None:
+            base, rep = self.base, rows // self.batch
+            max_new = self.max_len - self.base_len if max_new is None else max_new
+            assert max_new >= self.len - self.base_len
+            new = KVCache(len(self.qkv), rows, self.base_len + max_new, self.hidden, self.qkv[0].dtype, self.qkv[0].device, base=base)
+            n = self.len - self.base_len
+            for dst, src in zip(new.qkv, self.qkv):
+                dst[:, :n] = src[:, :n].repeat_interleave(rep, dim=0) if rep > 1 else src[:, :n]
+            new.len = self.len
+            if self.lens is not None:
+                new.lens = [l for l in self.lens for _ in range(rep)]
+            return new
+        if self.lens is not None:
+            raise NotImplementedError("KVCache.share: the base must be uniform (rows of one length); a ragged cache can only be fork()ed")
+        assert self.len > 0 and max_new is not None and max_new > 0, "KVCache.share: a non-empty base and room for new positions (max_new=)"
+        return KVCache(len(self.qkv), rows, self.len + max_new, self.hidden, self.qkv[0].dtype, self.qkv[0].device, base=self)
+
     def truncate(self, n):
         """forget the positions from n on (their rows are simply overwritten by the next extend / decode_step).  n: an int for every row, or a list with
-        one length per row (each at most what the row holds)"""
+        one length per row (each at most what the row holds).  A cache with a base keeps at least the base's positions."""
+        assert min(n) >= self.base_len if isinstance(n, (list, tuple)) else n >= self.base_len, "KVCache.truncate: cannot cut into the shared base"
         if isinstance(n, (list, tuple)):
             have = self.lens if self.lens is not None else [self.len] * self.batch
             assert len(n) == self.batch and all(0 <= int(a) <= h for a, h in zip(n, have))
@@ -278,6 +315,8 @@ class LlamaModel(nn.Module):
                 kv_len = hip.h2d(row_lens, dev)
         cos, sin = self.rope(S, dev)
         if cache is not None:
+            if cache.base is not None:
+                raise NotImplementedError("prefill into a KV cache with a shared base: its first positions are the base's (extend / decode_step append behind them)")
             assert cache.batch == B and cache.max_len >= S and cache.qkv[0].dtype == dt
             cache.len = S
             # a right-padded batch fills a RAGGED cache: the fused rows land where they always do, kv_len masks the pad keys as on the no-cache path, the pad
@@ -352,6 +391,16 @@ class LlamaModel(nn.Module):
             assert len(lengths) == B and all(1 <= n <= S for n in lengths)
             if len(set(lengths)) == 1 and lengths[0] == S:
                 lengths = None
+        if cache.base is not None:   # a shared base: the per-op body on hip.attention_shared (the one-call C stack entry does not know about bases)
+            layers = self.pack(dt)
+            x = inputs_embeds.reshape(B * S, D).float().clone()
+            cos, sin = self.rope(cache.max_len, inputs_embeds.device)
+            self.extend_layers_shared(x, layers, B, S, P, cos[P:P + S], sin[P:P + S], cache, dt, lengths)
+            cache.len = P + S
+            if lengths is not None:
+                cache.set_lens([P + n for n in lengths])
+            h16, h32 = hip.rmsnorm(x, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
+            return h32.view(B, S, D), h16
         if P == 0:
             mask = None if lengths is None else (torch.arange(S)[None, :] < torch.tensor(lengths)[:, None]).long()
             return self.prefill(inputs_embeds, mask, cache=cache)
@@ -390,6 +439,36 @@ class LlamaModel(nn.Module):
                      out=new, M=B * S, o_rows=(S, ML3), **_frag(pk, "wqkv"))
             a = hip.attention(new[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=S, Skv=P + S, D=hd, scale=hd ** -0.5, causal=True,
                               q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D), v_strides=(ML3, 3 * D), q_off=P, **({"kv_len": kv_len} if kv_len is not None else {}))
+            hip.gemm(a, pk["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
+            h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
+            g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, **_frag(pk, "wgu"))
+            hip.gemm(g, pk["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
+        return x
+
+    def extend_layers_shared(self, x, layers, B, S, pos, cos, sin, cache, dt, lengths=None):
+        """extend's layer loop for a cache with a shared base (KVCache.share): the S new rows sit at the local positions [off, off + S), off = pos - base_len,
+        of the cache's own buffers.  The QKV GEMM writes a dense [B * S, 3D] buffer — the 16-bit kernels behind hip.attention_shared walk the R * S query
+        rows of a group at ONE row stride — whose rows are then copied into the cache; the attention reads the base's P keys once per group and row b's own
+        off + S_b suffix keys (causal with the query offset `off`)."""
+        cfg = self.config
+        D = cfg.hidden_size
+        H = cfg.num_attention_heads
+        hd = D // H
+        base, P = cache.base, cache.base_len
+        off = pos - P
+        cap = cache.qkv[0].shape[1]
+        dev = x.device
+        sfx_len = None if lengths is None else hip.h2d(torch.tensor([off + n for n in lengths], dtype=torch.int32), dev)
+        dense = torch.empty((B * S, 3 * D), device=dev, dtype=dt)
+        for li_, pk in enumerate(layers):
+            h = self.qkv_operand(x, pk, dt) if "lora_A" in pk else hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)[0]
+            hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cos, sin), rope_seq=S, rope_cols=2 * D, out=dense, **_frag(pk, "wqkv"))
+            cache.qkv[li_][:, off:off + S].copy_(dense.view(B, S, 3 * D))
+            bq = base.qkv[li_].view(base.batch * base.max_len, 3 * D)
+            sq = cache.qkv[li_].view(B * cap, 3 * D)
+            a = hip.attention_shared(dense[:, :D], bq[:, D:2 * D], bq[:, 2 * D:], sq[:, D:2 * D], sq[:, 2 * D:], B=B, G=base.batch, H=H, Sq=S, P=P, D=hd,
+                                     scale=hd ** -0.5, max_sfx=off + S, sfx_len=sfx_len, sfx_q_off=off, causal=True, q_strides=(S * 3 * D, 3 * D),
+                                     kp_strides=(base.max_len * 3 * D, 3 * D), ks_strides=(cap * 3 * D, 3 * D))
             hip.gemm(a, pk["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
             h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
             g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, **_frag(pk, "wgu"))
@@ -496,6 +575,8 @@ class LlamaModel(nn.Module):
         dt = runtime.compute_dtype()
         if runtime.decode_weights() == "int8" and dt == torch.float32:
             raise NotImplementedError(f"int8 decode weights need a 16-bit compute mode (bf16 / fp16), not {runtime.mode_name()!r}")
+        if cache.base is not None and runtime.gemm_split():
+            raise NotImplementedError("decode_step on a KV cache with a shared base runs in the bf16 / fp16 / fp32 modes; fork() it for bf16x3 / mixed")
         layers = self.pack(dt)
         B, _, D = x_new.shape
         w8 = None
@@ -513,7 +594,19 @@ class LlamaModel(nn.Module):
         cos, sin = self.rope(cache.max_len, x_new.device)
         cpos, spos = cos[pos:pos + 1], sin[pos:pos + 1]
         rs, rg = 1, None
-        if cache.lens is not None:
+        if cache.base is not None:
+            # a shared base: ALWAYS the scratch-row route of the ragged step (one path for uniform and ragged suffixes) — RoPE at the total positions, the
+            # [k | v] columns appended at the LOCAL position lens[b] - P of the cache's own buffers, attention through hip.attention_shared (decode_attn)
+            dev = x_new.device
+            assert cache.batch == B
+            lens_, P_ = (cache.lens if cache.lens is not None else [pos] * B), cache.base_len
+            pos_d = hip.h2d(torch.tensor(lens_, dtype=torch.int32), dev)
+            cpos, spos = hip.gather_rows(cos, pos_d), hip.gather_rows(sin, pos_d)
+            rs = B
+            rg = dict(pos=hip.h2d(torch.tensor([n - P_ for n in lens_], dtype=torch.int32), dev),
+                      kv_len=hip.h2d(torch.tensor([n - P_ + 1 for n in lens_], dtype=torch.int32), dev), max_kv=pos - P_ + 1,
+                      scratch=torch.empty((B, 3 * D), device=dev, dtype=dt))
+        elif cache.lens is not None:
             # ragged step: token b sits at position lens[b].  The RoPE epilogues take pos = row % rope_seq, so B table rows cos[lens[b]] with rope_seq = B
             # need no GEMV change; the positions / lengths travel through the pinned ring (the host knows them: no device synchronisation).  The QKV
             # GEMV writes rows at ONE stride only -> a dense [B, 3D] scratch row, scattered into the cache by kv_append_rows (decode_attn)
@@ -551,7 +644,7 @@ class LlamaModel(nn.Module):
                 h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
                 g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU)
             hip.gemm(g, pk["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
-        if rg is None:
+        if rg is None or cache.lens is None:
             cache.len = pos + 1
         else:
             cache.lens = [n + 1 for n in cache.lens]
@@ -567,6 +660,17 @@ class LlamaModel(nn.Module):
         B, D = row.shape[0], row.shape[1] // 3
         H = self.config.num_attention_heads
         hd = D // H
+        if cache.base is not None:
+            # shared base (rg: decode_step's tables in LOCAL positions): append to the cache's own rows, then every group of rows reads the base's P keys
+            # once and each row its own suffix (bf16 / fp16: the shared-prefix decode kernels, 2 launches; fp32: the vector kernel).  No other kernel runs
+            # in their place: an unsupported head_dim is an error of the C entry point
+            base, cap = cache.base, cache.qkv[li_].shape[1]
+            hip.kv_append_rows(row, cache.qkv[li_], rg["pos"])
+            bq = base.qkv[li_].view(base.batch * base.max_len, 3 * D)
+            sq = cache.qkv[li_].view(B * cap, 3 * D)
+            return hip.attention_shared(row[:, :D], bq[:, D:2 * D], bq[:, 2 * D:], sq[:, D:2 * D], sq[:, 2 * D:], B=B, G=base.batch, H=H, Sq=1,
+                                        P=cache.base_len, D=hd, scale=hd ** -0.5, max_sfx=rg["max_kv"], sfx_len=rg["kv_len"], q_strides=(3 * D, 3 * D),
+                                        kp_strides=(base.max_len * 3 * D, 3 * D), ks_strides=(cap * 3 * D, 3 * D))
         ML3 = cache.max_len * 3 * D
         full = cache.qkv[li_].view(B * cache.max_len, 3 * D)
         if rg is None:
@@ -615,6 +719,8 @@ class LlamaModel(nn.Module):
             out = Output(last_hidden_state=hidden, past_key_values=None, hidden_states=(hidden,) if output_hidden_states else None, attentions=None)
             out._h16, out._sp_rows = h16, rows
             return out
+        if isinstance(past_key_values, KVCache) and past_key_values.base is not None:
+            raise NotImplementedError("forward(past_key_values=) with a KV cache that has a shared base: use extend / decode_step, or fork() it")
         if isinstance(past_key_values, KVCache) and past_key_values.len > 0:   # decode step(s), one token at a time
             hs = []
             for t in range(inputs_embeds.shape[1]):

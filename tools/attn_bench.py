@@ -57,6 +57,59 @@ if "--ragged" in sys.argv:
               f"ragged {min(res['ragged']):6.1f} us ({res['ragged'][0]:.1f} {res['ragged'][1]:.1f})  kv_append_rows {min(res['append']):5.1f} us ({res['append'][0]:.1f} {res['append'][1]:.1f})"
               f"  keys read {sum(lens)} vs {B * L}  -> {kern}", flush=True)
     sys.exit(0)
+if "--shared" in sys.argv:
+    # --shared R,P[,sfx] (repeatable): the one-token decode attention of R rows that share one P-key prefix and own sfx keys each (default 64).
+    #   shared : hip.attention_shared — the prefix is read once for the R rows (dedicated prefix workgroups + suffix workgroups, then the merge);
+    #   copies : the ragged decode attention on R private copies of prefix + suffix (what fork() gives), P + sfx keys per row;
+    #   split  : the existing key-split tile kernel + its merge over the PREFIX ONLY, as a non-causal problem with R query rows (what the dedicated prefix
+    #            workgroups replace; no suffix, no second merge: a lower bound of a composed decode path).
+    # Same process, alternating, every timing a captured graph of 20 calls; best of 5 replays, both rounds printed.
+    def timed_s(fn, rounds=5):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(20):
+                fn()
+        g.replay(); torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        best = float("inf")
+        for _ in range(rounds):
+            s.record(); g.replay(); e.record(); torch.cuda.synchronize()
+            best = min(best, s.elapsed_time(e) / 20 * 1e3)
+        return best
+    H, D, dt = 32, 128, torch.bfloat16
+    W = 3 * H * D
+    for spec in [sys.argv[i + 1] for i, a in enumerate(sys.argv) if a == "--shared"]:
+        R, P, sfx = (list(map(int, spec.split(","))) + [64])[:3]
+        MLp, MLs, MLc = P + 8, sfx + 8, P + sfx + 8
+        pre = torch.randn(MLp, W, device="cuda").to(dt)
+        suf = torch.randn(R * MLs, W, device="cuda").to(dt)
+        cop = torch.randn(R * MLc, W, device="cuda").to(dt)
+        row = torch.randn(R, W, device="cuda").to(dt)
+        out = torch.empty(R, H * D, device="cuda", dtype=dt)
+        sl = torch.full((R,), sfx, dtype=torch.int32).cuda()
+        kl = torch.full((R,), P + sfx, dtype=torch.int32).cuda()
+        shared = lambda: hip.attention_shared(row[:, :H * D], pre[:, H * D:2 * H * D], pre[:, 2 * H * D:], suf[:, H * D:2 * H * D], suf[:, 2 * H * D:], B=R, G=1, H=H,
+                                              Sq=1, P=P, D=D, scale=D ** -0.5, max_sfx=sfx, sfx_len=sl, q_strides=(W, W), kp_strides=(MLp * W, W),
+                                              ks_strides=(MLs * W, W), out=out)
+        copies = lambda: hip.attention(row[:, :H * D], cop[:, H * D:2 * H * D], cop[:, 2 * H * D:], B=R, H=H, Sq=1, Skv=P + sfx, D=D, scale=D ** -0.5, kv_len=kl,
+                                       q_strides=(W, W), k_strides=(MLc * W, W), v_strides=(MLc * W, W), out=out)
+        split = lambda: hip.attention(row[:, :H * D], pre[:, H * D:2 * H * D], pre[:, 2 * H * D:], B=1, H=H, Sq=R, Skv=P, D=D, scale=D ** -0.5, causal=False,
+                                      q_strides=(R * W, W), k_strides=(MLp * W, W), v_strides=(MLp * W, W), q_off=1, out=out)
+        res = {}
+        hip.set_option("attn_ksplit", 1)
+        try:
+            for rnd in range(3):
+                for name, f in (("shared", shared), ("copies", copies), ("split", split)):
+                    res.setdefault(name, []).append(timed_s(f))
+        finally:
+            hip.set_option("attn_ksplit", -1)
+        fmt = lambda n: f"{min(res[n]):6.1f} us (" + " ".join(f"{x:.1f}" for x in res[n]) + ")"
+        print(f"shared-prefix decode attention R={R:3d} P={P:5d} sfx={sfx:4d}: shared {fmt('shared')}  copies {fmt('copies')}  prefix-only key-split+merge {fmt('split')}"
+              f"  K/V bytes shared {(P + R * sfx) * 2 * H * D * 2 / 1e6:.1f} MB vs copies {R * (P + sfx) * 2 * H * D * 2 / 1e6:.1f} MB", flush=True)
+    sys.exit(0)
 if "--suffix" in sys.argv:
     # LlamaModel.extend's shape: Sq new rows behind q_off cached ones, operands addressed inside one fused cache buffer as the model passes them.
     # The offset tile kernel (attn_ksplit = 0) and the key-split pair (1) on the same buffers, same process, alternating; "auto" is the dispatch rule.

@@ -18,6 +18,10 @@ ap.add_argument("--attn-single", type=int, default=1, help="stllm_set_option('at
 ap.add_argument("--ragged", default="", help="L1,L2,...: time ragged steps at these per-row cache lengths against uniform steps with every row at max(L), alternating")
 ap.add_argument("--questions", default="", help="L1,L2,...: N questions of these lengths behind one prefilled 576-token prefix — generate(batching='ragged') in one "
                                                 "batch against one generate() per question (what a padded batch behind a prefix costs without the ragged cache)")
+ap.add_argument("--share-prefix", action="store_true", help="with --questions or --beams: generate(share_prefix=True) against share_prefix=False (private copies), "
+                                                          "alternating; tokens/s and peak memory_allocated of both")
+ap.add_argument("--beams", type=int, default=0, help="with --share-prefix: one prompt of --prefix-len + 24 positions, this many beams (5 = demo.py)")
+ap.add_argument("--prefix-len", type=int, default=576, help="positions of the shared prefix of --share-prefix")
 args = ap.parse_args()
 torch.set_grad_enabled(False)
 dev = torch.device("cuda:0")
@@ -98,6 +102,44 @@ def questions_e2e(lens):
               f"= {N * args.tokens / t:.1f} tok/s (runs {' '.join(f'{x * 1e3:.1f}' for x in ts)})")
 
 
+def share_prefix_e2e(lens, beams):
+    """generate() with share_prefix off / on, alternating, 3 runs each (the first warms up): N questions of `lens` behind one prefilled prefix in one ragged
+    batch, or (beams) one whole prompt with that many beams — there the prompt's own cache is the base.  eos disabled: both emit the same number of ids."""
+    P = args.prefix_len
+    video = torch.randn(1, P, 4096, device=dev) * 0.02
+    if beams:
+        kw = dict(inputs_embeds=torch.cat([video, torch.randn(1, 24, 4096, device=dev) * 0.02], dim=1), num_beams=beams)
+        what, n_tok = f"{beams} beams behind {P + 24} prompt positions", args.tokens
+    else:
+        prefix = lm.new_cache(1, P, dev)
+        lm.prefill(video, None, cache=prefix)
+        N = len(lens)
+        emb = torch.zeros(N, max(lens), 4096, device=dev)
+        mask = torch.zeros(N, max(lens), dtype=torch.long)
+        for i, n in enumerate(lens):
+            emb[i, :n] = torch.randn(n, 4096, device=dev) * 0.02
+            mask[i, :n] = 1
+        kw = dict(inputs_embeds=emb, attention_mask=mask, batching="ragged", prefix_cache=prefix)
+        what, n_tok = f"{N} questions (lens {','.join(map(str, lens))}) behind a {P}-token prefix", N * args.tokens
+    res, peak = {}, {}
+    for share in (False, True) * 3:
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        m0 = torch.cuda.memory_allocated()
+        t0 = time.perf_counter()
+        model.generate(max_new_tokens=args.tokens, eos_token_id=None, share_prefix=share, **kw)
+        torch.cuda.synchronize()
+        res.setdefault(share, []).append(time.perf_counter() - t0)
+        peak[share] = torch.cuda.max_memory_allocated() - m0
+    for share, ts in res.items():
+        t = min(ts[1:])
+        print(f"{what}, {args.tokens} new tokens, weights {args.weights} [share_prefix={share}]: {t * 1e3:.1f} ms = {n_tok / t:.1f} tok/s "
+              f"(runs {' '.join(f'{x * 1e3:.1f}' for x in ts)}), peak memory above the model + prefix {peak[share] / 1e6:.0f} MB", flush=True)
+
+
+if args.share_prefix:
+    share_prefix_e2e([int(x) for x in args.questions.split(",")] if args.questions else [], args.beams)
+    sys.exit(0)
 if args.ragged:
     ragged_steps([int(x) for x in args.ragged.split(",")])
     sys.exit(0)

@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--new", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--mode", default="bf16")
+    ap.add_argument("--share-prefix", action="store_true", help="add (d): first token / answer with the prefix SHARED (KVCache.share, generate(share_prefix=True)) "
+                                                                "instead of forked: no copy of the prefix rows, the shared-prefix attention kernels")
     a = ap.parse_args()
     import stllm_amd  # noqa: F401
     import bench
@@ -76,6 +78,13 @@ def main():
         ans_a = lambda: m.generate(inputs_embeds=whole, **kw)
         ans_b = lambda: m.generate(inputs_embeds=q_emb, prefix_cache=prefix, **kw)
         fns = dict(first_a=first_a, first_b=first_b, first_c=first_c, ans_a=ans_a, ans_b=ans_b)
+        if a.share_prefix:
+            def first_d():
+                c = prefix.share(max_new=Q + N)
+                _, h = lm.extend(q_emb, c)
+                return m.logits_from(h.view(1, Q, -1)[:, -1].contiguous(), 1, 1)
+            fns.update(first_d=first_d, ans_d=lambda: m.generate(inputs_embeds=q_emb, prefix_cache=prefix, share_prefix=True, **kw))
+            fns["ans_d"]()
         ids_a, ids_b = ans_a(), ans_b()                       # warm-up of every path (packing, workspaces, allocator) + a sanity line
         first_c()
         same = int((ids_a == ids_b).sum())
