@@ -221,6 +221,40 @@ typedef struct {
 } stllm_gemv_w8_args;
 int stllm_gemv_w8(const stllm_gemv_w8_args* args, void* stream);
 
+/*
+ * W4A16 skinny GEMM of the decode regime (st-llm_amd/csrc/gemv.hip), ABI version >= 7 (additive):
+ *   C[M,N] = epilogue(sum_g scale[n,g] * (A[M, 128 g : 128 g + 128] @ q[n, 128 g : 128 g + 128]^T) + bias[n])
+ * A: bf16 / fp16 [M,lda]; Wq: uint8 [N,ldw] (ldw in BYTES, >= K / 2), two 4-bit weights per byte, stored nibble u = q + 8 in [1, 15] (|q| <= 7),
+ * rows packed like the 16-bit weight they were quantised from (st-llm_amd/pack.py: quant4_groups after llama_qkv / llama_gate_up / linear).
+ * Nibble placement: dword d of a row holds elements 8 d .. 8 d + 7; element 2 t at bits [4 t, 4 t + 4), element 2 t + 1 at bits [16 + 4 t, 16 + 4 t + 4).
+ * scale: f32 [N, ld_scale], one per output row and group of 128 K elements (ld_scale >= K / 128, in floats).
+ * The accumulation is fp32 over exact products (q, or the exact offset form 136 + q whose offset is removed in fp32); the scale multiplies the finished
+ * sum of its group, before bias / residual / SwiGLU / RoPE.  Wq and scale are read-only.
+ * Epilogues, 2-level row indexing, strided output rows and a_norm_* (M <= 2): those of stllm_gemv_w8.
+ * Kernels: M <= 2 (option "gemv_mfma" = 0: M <= 8) the VALU kernel (the staged rows of A, 1 / 2 / 4 / 6 / 8 x K x 2 bytes, must fit 150 KiB of LDS);
+ * 3 <= M <= 16 ("gemv_mfma" = 1: from M = 1) the matrix-core kernel.
+ * Constraints: 1 <= M <= 16; N % 64 == 0; K % 128 == 0; Wq 16-byte aligned, ldw % 16 == 0; A / out / resid as for stllm_gemm.
+ * A shape or option combination no kernel covers returns STLLM_ERR_UNSUPPORTED (stllm_last_error() says which): nothing else runs in its place.
+ * Launches are seen by stllm_gemm_profile; stllm_last_kernel() names gemv_q4_kernel<...> / gemv_q4_mfma_kernel<...>.
+ */
+typedef struct {
+  int dtype;          /* STLLM_BF16 | STLLM_F16: A and the 16-bit outputs */
+  int epilogue;       /* STORE | RESID | SWIGLU | ROPE */
+  int out_is_f32;     /* STORE only */
+  int M, N, K;
+  const void* A; int64_t lda;            /* elements; ignored with a_norm_x */
+  const void* Wq; int64_t ldw;           /* packed nibbles, row stride in bytes */
+  const float* scale; int64_t ld_scale;  /* f32 [N, K / 128], row stride in floats */
+  const float* bias;                     /* f32 [N] or NULL */
+  void* out; int64_t ldo;
+  const float* resid; int64_t ldr;
+  const float* rope_cos; const float* rope_sin; int rope_seq; int rope_cols;
+  int a_rows_per_batch; int64_t a_batch_stride;
+  int o_rows_per_batch; int64_t o_batch_stride;
+  const float* a_norm_x; int64_t a_norm_ldx; const float* a_norm_gamma; float a_norm_eps;
+} stllm_gemv_q4_args;
+int stllm_gemv_q4(const stllm_gemv_q4_args* args, void* stream);
+
 /* HIP-event timing of stllm_gemm launches on their launch stream, per calling thread (bench.py's roofline leg; also sees the launches of
  * the whole-stack entry points below).  mode 0 off | 1 every launch | 2 only launches whose kernel symbol — learned per (dtype, epilogue,
  * act, M, N, K) while mode 1 was on — equals target_symbol | 3 every 7th of those (a sample: the event records sit between the kernels on

@@ -27,7 +27,7 @@ EXPORTS = ["stllm_last_error", "stllm_abi_version", "stllm_last_kernel", "stllm_
            "stllm_vit_blocks_scratch_bytes", "stllm_vit_blocks", "stllm_llama_layers_scratch_bytes", "stllm_llama_layers", "stllm_llama_layer_sp_scratch_bytes", "stllm_llama_layer_sp",
            "stllm_qformer_layers_scratch_bytes", "stllm_qformer_layers", "stllm_split3_rows", "stllm_gemm_split_ws_bytes",
            "stllm_lora_down_workspace_bytes", "stllm_lora_down", "stllm_llama_layers_lora_scratch_bytes", "stllm_llama_layers_lora",
-           "stllm_attention_offset_workspace_bytes", "stllm_attention_offset", "stllm_llama_layers_extend", "stllm_gemv_w8",
+           "stllm_attention_offset_workspace_bytes", "stllm_attention_offset", "stllm_llama_layers_extend", "stllm_gemv_w8", "stllm_gemv_q4",
            "stllm_attention_decode_ragged_workspace_bytes", "stllm_attention_decode_ragged", "stllm_kv_append_rows",
            "stllm_attention_shared_workspace_bytes", "stllm_attention_shared"]
 
@@ -57,6 +57,15 @@ class GemmArgs(ctypes.Structure):
 class GemvW8Args(ctypes.Structure):
     _fields_ = [("dtype", c_int), ("epilogue", c_int), ("out_is_f32", c_int), ("M", c_int), ("N", c_int), ("K", c_int),
                 ("A", c_void_p), ("lda", c_int64), ("Wq", c_void_p), ("ldw", c_int64), ("scale", c_void_p), ("bias", c_void_p),
+                ("out", c_void_p), ("ldo", c_int64), ("resid", c_void_p), ("ldr", c_int64),
+                ("rope_cos", c_void_p), ("rope_sin", c_void_p), ("rope_seq", c_int), ("rope_cols", c_int),
+                ("a_rows_per_batch", c_int), ("a_batch_stride", c_int64), ("o_rows_per_batch", c_int), ("o_batch_stride", c_int64),
+                ("a_norm_x", c_void_p), ("a_norm_ldx", c_int64), ("a_norm_gamma", c_void_p), ("a_norm_eps", c_float)]
+
+
+class GemvQ4Args(ctypes.Structure):
+    _fields_ = [("dtype", c_int), ("epilogue", c_int), ("out_is_f32", c_int), ("M", c_int), ("N", c_int), ("K", c_int),
+                ("A", c_void_p), ("lda", c_int64), ("Wq", c_void_p), ("ldw", c_int64), ("scale", c_void_p), ("ld_scale", c_int64), ("bias", c_void_p),
                 ("out", c_void_p), ("ldo", c_int64), ("resid", c_void_p), ("ldr", c_int64),
                 ("rope_cos", c_void_p), ("rope_sin", c_void_p), ("rope_seq", c_int), ("rope_cols", c_int),
                 ("a_rows_per_batch", c_int), ("a_batch_stride", c_int64), ("o_rows_per_batch", c_int), ("o_batch_stride", c_int64),
@@ -183,6 +192,7 @@ def _bind(L, strict=True):
     B("stllm_attention_offset", [c_int] + [c_void_p, c_int64, c_int64] * 4 + [c_int] * 5 + [c_float, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_llama_layers_extend", [ctypes.POINTER(LlamaLayersArgs), ctypes.POINTER(LlamaLayerWeights), c_int, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_gemv_w8", [ctypes.POINTER(GemvW8Args), c_void_p])
+    B("stllm_gemv_q4", [ctypes.POINTER(GemvQ4Args), c_void_p])
     B("stllm_gemm_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     B("stllm_gemm_w4_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     return L
@@ -628,6 +638,68 @@ def gemv_w8(a, wq, scale, *, dtype, epilogue=EPI_STORE, bias=None, resid=None, r
     args.out, args.ldo = _p(out), out.stride(-2)
     args.M, args.N, args.K = M, N, K
     _check(lib().stllm_gemv_w8(ctypes.byref(args), _stream()), "stllm_gemv_w8")
+    return out
+
+
+def gemv_q4(a, qp, scale, *, dtype, epilogue=EPI_STORE, bias=None, resid=None, rope=None, rope_seq=0, rope_cols=0, out=None, out_f32=False,
+            a_norm=None, M=None, a_rows=None, o_rows=None):
+    """out = epilogue(sum_g scale[:, g] * (a[:, g] @ q[:, g].T) + bias) for the decode regime (M <= 16): a [M,K] bf16 / fp16, (qp uint8 [N,K/2],
+    scale f32 [N,K/128]) = pack.quant4_groups of the packed 16-bit weight (q: pack.dequant4_groups) — stllm_gemv_q4 (stllm_hip.h).  The scale is applied
+    per 128-element K group to the finished group sum, before bias / residual / SwiGLU / RoPE.  Epilogues, a_norm (M <= 2), a_rows / o_rows as in
+    gemv_w8.  A shape no 4-bit kernel covers raises (nothing else runs in its place)."""
+    td = torch_dtype(dtype)
+    if td not in (torch.bfloat16, torch.float16):
+        raise RuntimeError(f"gemv_q4: 16-bit activations only, got {td}")
+    if epilogue not in (EPI_STORE, EPI_RESID, EPI_SWIGLU, EPI_ROPE):
+        raise RuntimeError(f"gemv_q4: epilogue {epilogue} is not STORE / RESID / SWIGLU / ROPE")
+    args = GemvQ4Args()
+    args.dtype, args.epilogue, args.out_is_f32 = dtype_code(td), epilogue, int(out_f32)
+    _req(qp, torch.uint8, "Wq"); _req(scale, torch.float32, "scale")
+    N = qp.shape[0]
+    if a_norm is not None:
+        xn, gamma, eps = a_norm
+        _req(xn, torch.float32, "a_norm x"); _req(gamma, torch.float32, "a_norm gamma")
+        K = xn.shape[-1]
+        M = xn.shape[0] if M is None else M
+        args.a_norm_x, args.a_norm_ldx, args.a_norm_gamma, args.a_norm_eps = _p(xn), xn.stride(-2), _p(gamma), float(eps)
+    else:
+        _req(a, td, "A")
+        K = a.shape[-1]
+        if a_rows is not None:
+            args.a_rows_per_batch, args.a_batch_stride = a_rows
+            if M is None:
+                raise RuntimeError("gemv_q4: M is required with a_rows")
+        elif M is None:
+            M = a.shape[0]
+        args.A, args.lda = _p(a), a.stride(-2)
+    if qp.shape[1] * 2 != K:
+        raise RuntimeError(f"gemv_q4: Wq holds {qp.shape[1] * 2} weights per row, A has K = {K}")
+    if scale.dim() != 2 or tuple(scale.shape) != (N, -(-K // 128)):
+        raise RuntimeError(f"gemv_q4: scale must be f32 [{N}, {-(-K // 128)}]")
+    args.Wq, args.ldw, args.scale, args.ld_scale = _p(qp), qp.stride(0), _p(scale), scale.stride(0)
+    if bias is not None:
+        _req(bias, torch.float32, "bias")
+    args.bias = _p(bias)
+    if epilogue == EPI_RESID:
+        _req(resid, torch.float32, "resid")
+        out = resid if out is None else out
+        _req(out, torch.float32, "out")
+        args.resid, args.ldr = _p(resid), resid.stride(-2)
+    else:
+        n_out = N // 2 if epilogue == EPI_SWIGLU else N
+        odt = torch.float32 if (out_f32 and epilogue == EPI_STORE) else td
+        if out is None:
+            out = torch.empty((M, n_out), device=qp.device, dtype=odt)
+        _req(out, odt, "out")
+    if epilogue == EPI_ROPE:
+        cos, sin = rope
+        _req(cos, torch.float32, "rope cos"); _req(sin, torch.float32, "rope sin")
+        args.rope_cos, args.rope_sin, args.rope_seq, args.rope_cols = _p(cos), _p(sin), rope_seq, rope_cols
+    if o_rows is not None:
+        args.o_rows_per_batch, args.o_batch_stride = o_rows
+    args.out, args.ldo = _p(out), out.stride(-2)
+    args.M, args.N, args.K = M, N, K
+    _check(lib().stllm_gemv_q4(ctypes.byref(args), _stream()), "stllm_gemv_q4")
     return out
 
 

@@ -20,6 +20,10 @@ Int8 decode weights (runtime.set_decode_weights("int8")): decode_step streams an
 layer (pack.quant8_rows: one fp32 scale per output row) through the W8A16 kernels (hip.gemv_w8) — half the bytes per token.  The copy lives
 NEXT TO the 16-bit weights, which prefill / extend keep using: + 6.6 GB at 7B on top of the 13.5 GB of the 16-bit pack.  This is the
 reference's `device_8bit` knob (demo.py:41) with something behind it.
+
+Int4 decode weights (runtime.set_decode_weights("int4g128")): the same routing over a 4-bit copy (pack.quant4_groups: two weights per byte, one fp32 scale
+per output row and group of 128 K elements) on the W4A16 kernels (hip.gemv_q4) — about 0.27 of the 16-bit bytes per token, + 3.5 GB at 7B.  One quantised
+copy exists at a time: switching between "int8", "int4g128" and None frees the other at the next decode_step.
 """
 import os
 
@@ -209,6 +213,7 @@ class LlamaModel(nn.Module):
         self.norm = RMSNorm(config.hidden_size, config.rms_norm_eps, device)
         self._packed = {}
         self._packed_w8 = {}   # dt -> (fingerprint, per-layer {wqkv, wo, wgu, wdown: (q int8, scale f32)}): the int8 decode weights, built on first use
+        self._packed_q4 = {}   # dt -> (fingerprint, per-layer {wqkv, wo, wgu, wdown: (qp uint8 [N, K/2], scale f32 [N, K/128])}): the 4-bit decode weights
         self._rope = {}
         self._carr = {}   # C-side table of the packed layers (+ the cache it points into): rebuilt when either changes
         self._plist = ParamList(lambda: self.layers.parameters())
@@ -242,8 +247,24 @@ class LlamaModel(nn.Module):
         hit = self._packed_w8.get(dt)
         if hit is None or hit[0] != fp:
             self._packed_w8 = {}   # one copy at a time
+            self._packed_q4 = {}
             hit = (fp, [{k: pack.quant8_rows(pk[k]) for k in ("wqkv", "wo", "wgu", "wdown")} for pk in layers])
             self._packed_w8[dt] = hit
+        return hit[1]
+
+    def pack_q4(self, dtype=None):
+        """the 4-bit decode weights: per layer {wqkv, wo, wgu, wdown} -> (qp uint8 [N, K / 2], scale f32 [N, K / 128]) = pack.quant4_groups of the packed
+        16-bit weights of pack(dt); cached, rebuilt and dropped exactly as pack_w8's copy is (same fingerprint, repack(), state-dict loads, the mode
+        switched away from "int4g128").  Building it drops the int8 copy: one quantised copy at a time.  + 3.5 GB at 7B."""
+        dt = hip.torch_dtype(dtype) if dtype is not None else runtime.compute_dtype()
+        layers = self.pack(dt)
+        fp = self._packed[dt][0]
+        hit = self._packed_q4.get(dt)
+        if hit is None or hit[0] != fp:
+            self._packed_q4 = {}   # one copy at a time
+            self._packed_w8 = {}
+            hit = (fp, [{k: pack.quant4_groups(pk[k]) for k in ("wqkv", "wo", "wgu", "wdown")} for pk in layers])
+            self._packed_q4[dt] = hit
         return hit[1]
 
     def add_lora(self, r, lora_alpha=32):
@@ -268,12 +289,14 @@ class LlamaModel(nn.Module):
     def repack(self):
         self._packed = {}
         self._packed_w8 = {}
+        self._packed_q4 = {}
         self._carr = {}
         self._plist.reset()
 
     def _load_from_state_dict(self, *a, **k):
         self._packed = {}
         self._packed_w8 = {}
+        self._packed_q4 = {}
         self._carr = {}
         self._plist.reset()
         return super()._load_from_state_dict(*a, **k)
@@ -573,20 +596,26 @@ class LlamaModel(nn.Module):
         cache and returns (hidden f32 [B,1,D] after model.norm, hidden compute-dtype [B,D])."""
         cfg = self.config
         dt = runtime.compute_dtype()
-        if runtime.decode_weights() == "int8" and dt == torch.float32:
-            raise NotImplementedError(f"int8 decode weights need a 16-bit compute mode (bf16 / fp16), not {runtime.mode_name()!r}")
+        wmode = runtime.decode_weights()
+        if wmode is not None and dt == torch.float32:
+            raise NotImplementedError(f"{wmode} decode weights need a 16-bit compute mode (bf16 / fp16), not {runtime.mode_name()!r}")
         if cache.base is not None and runtime.gemm_split():
             raise NotImplementedError("decode_step on a KV cache with a shared base runs in the bf16 / fp16 / fp32 modes; fork() it for bf16x3 / mixed")
         layers = self.pack(dt)
         B, _, D = x_new.shape
-        w8 = None
-        if runtime.decode_weights() == "int8":
+        w8 = q4 = None
+        if wmode is not None:
             if "lora_A" in layers[0]:
-                raise NotImplementedError("int8 decode weights with active LoRA adapters: merge_adapter() first")
-            if B <= 16:   # the decode regime of hip.gemv_w8; larger batches stream the 16-bit weights on the tile kernels
-                w8 = self.pack_w8(dt)
-        elif self._packed_w8:
-            self._packed_w8 = {}   # the mode was switched off: free the int8 copy
+                raise NotImplementedError(f"{wmode} decode weights with active LoRA adapters: merge_adapter() first")
+            if B <= 16:   # the decode regime of hip.gemv_w8 / hip.gemv_q4; larger batches stream the 16-bit weights on the tile kernels
+                if wmode == "int8":
+                    w8 = self.pack_w8(dt)
+                else:
+                    q4 = self.pack_q4(dt)
+        if wmode != "int8" and self._packed_w8:
+            self._packed_w8 = {}   # the mode was switched away: free the int8 copy
+        if wmode != "int4g128" and self._packed_q4:
+            self._packed_q4 = {}   # likewise the 4-bit copy
         H = cfg.num_attention_heads
         hd = D // H
         pos = cache.len
@@ -627,6 +656,9 @@ class LlamaModel(nn.Module):
             row = cache.qkv[li_][:, pos] if rg is None else rg["scratch"]   # [B, 3D]: a view of the cache, row stride max_len*3D | the dense scratch
             if w8 is not None:   # the same step over the int8 weights (W8A16 kernels): same epilogues, same fused norms
                 self.decode_layer_w8(x, pk, w8[li_], row, cache, li_, pos, cpos, spos, fuse and B <= 2, dt, rope_seq=rs, rg=rg)   # (stllm_gemv_w8 fuses the norm for <= 2 rows)
+                continue
+            if q4 is not None:   # likewise over the 4-bit weights (W4A16 kernels)
+                self.decode_layer_q4(x, pk, q4[li_], row, cache, li_, pos, cpos, spos, fuse and B <= 2, dt, rope_seq=rs, rg=rg)   # (stllm_gemv_q4 fuses the norm for <= 2 rows)
                 continue
             if "lora_A" in pk:   # active adapters: the fused-RMSNorm GEMV cannot see t = h A^T — norm, down projection, then the GEMV over K = D + P
                 hip.gemm(self.qkv_operand(x, pk, dt), pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rs, rope_cols=2 * D, out=row)
@@ -688,22 +720,30 @@ class LlamaModel(nn.Module):
 
     def decode_layer_w8(self, x, pk, q8, row, cache, li_, pos, cpos, spos, fuse, dt, rope_seq=1, rg=None):
         """one decoder layer of decode_step with its four projections on hip.gemv_w8 (q8: pack_w8's entry of the layer); attention and norms as in the 16-bit step"""
+        self.decode_layer_quant(hip.gemv_w8, x, pk, q8, row, cache, li_, pos, cpos, spos, fuse, dt, rope_seq, rg)
+
+    def decode_layer_q4(self, x, pk, q4, row, cache, li_, pos, cpos, spos, fuse, dt, rope_seq=1, rg=None):
+        """the same layer on hip.gemv_q4 (q4: pack_q4's entry of the layer)"""
+        self.decode_layer_quant(hip.gemv_q4, x, pk, q4, row, cache, li_, pos, cpos, spos, fuse, dt, rope_seq, rg)
+
+    def decode_layer_quant(self, gemv, x, pk, qw, row, cache, li_, pos, cpos, spos, fuse, dt, rope_seq, rg):
+        """the shared body: gemv(a, q, scale, ...) is hip.gemv_w8 or hip.gemv_q4 (one signature), qw the layer's {name: (q, scale)}"""
         cfg = self.config
         B, D = x.shape
         if fuse:
-            hip.gemv_w8(None, *q8["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rope_seq, rope_cols=2 * D, out=row,
-                        a_norm=(x, pk["ln1"], cfg.rms_norm_eps))
+            gemv(None, *qw["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rope_seq, rope_cols=2 * D, out=row,
+                 a_norm=(x, pk["ln1"], cfg.rms_norm_eps))
         else:
             h, _ = hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)
-            hip.gemv_w8(h, *q8["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rope_seq, rope_cols=2 * D, out=row)
+            gemv(h, *qw["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rope_seq, rope_cols=2 * D, out=row)
         a = self.decode_attn(row, cache, li_, pos, rg)
-        hip.gemv_w8(a, *q8["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
+        gemv(a, *qw["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
         if fuse:
-            g = hip.gemv_w8(None, *q8["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, a_norm=(x, pk["ln2"], cfg.rms_norm_eps))
+            g = gemv(None, *qw["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, a_norm=(x, pk["ln2"], cfg.rms_norm_eps))
         else:
             h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
-            g = hip.gemv_w8(h, *q8["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU)
-        hip.gemv_w8(g, *q8["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
+            g = gemv(h, *qw["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU)
+        gemv(g, *qw["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
 
     def new_cache(self, batch, max_len, device):
         return KVCache(len(self.layers), batch, max_len, self.config.hidden_size, runtime.compute_dtype(), device)

@@ -16,6 +16,8 @@ parameter lives on); none changes the mathematical function:
 * ``bert_qkv`` / ``bert_kv`` — Q-Former query/key/value fused (Qformer.py:127-133).
 * ``quant8_rows``    — the one packer that is NOT exact: a packed 16-bit weight -> int8 rows + one fp32 scale per row, the
                        weight format of the W8A16 decode kernels (hip.gemv_w8).
+* ``quant4_groups``  — its 4-bit sibling: two weights per byte + one fp32 scale per row and 128-element K group, the weight
+                       format of the W4A16 decode kernels (hip.gemv_q4); ``dequant4_groups`` undoes the nibble placement.
 """
 import os
 
@@ -100,6 +102,43 @@ def quant8_rows(w16):
     scale = torch.where(amax > 0, amax / 127.0, torch.ones_like(amax))
     q = torch.clamp(torch.round(wf.double() / scale.double()[:, None]), -127.0, 127.0).to(torch.int8)
     return q.contiguous(), scale.contiguous()
+
+
+Q4_GROUP = 128
+_Q4_LO, _Q4_HI = (0, 4, 1, 5), (2, 6, 3, 7)   # elements of an 8-element piece in the low / high nibbles of its 4 bytes
+
+
+def quant4_groups(w16, group=Q4_GROUP):
+    """packed weight [N, K] (K % 128 == 0) -> (qp uint8 [N, K / 2] contiguous, scale f32 [N, K / 128] contiguous) for hip.gemv_q4: symmetric, one
+    scale per output row and group of 128 consecutive K elements.  amax = max |w| over the group (fp32); scale = amax / 7, an fp32 division (1 for an
+    all-zero group); q = clamp(rint(w / scale), -7, 7), round-half-even, the quotient taken in fp64 for the reason given in quant8_rows (so
+    |w - q scale| <= scale / 2 (1 + 2^-20)); -8 never occurs.  Stored nibble u = q + 8 in [1, 15].
+    Nibble placement, a fixed permutation inside every 8-element piece (so every 8-, 32- or 128-aligned slice of K is self-contained): read as a
+    little-endian dword, the 4 bytes of piece j hold element 8 j + 2 t at bits [4 t, 4 t + 4) and element 8 j + 2 t + 1 at bits [16 + 4 t, 16 + 4 t + 4),
+    t = 0..3 — byte b carries the elements (0, 2), (4, 6), (1, 3), (5, 7)[b] in its (low, high) nibble.  In a register `(w >> 4 t) & 0x000f000f` is then
+    the K-adjacent pair t with one nibble at the bottom of each 16-bit half, ready to have a float exponent or-ed onto it (csrc/gemv.hip, Q4).
+    Only this function, dequant4_groups and the kernel know the placement.  Like quant8_rows it works on the PACKED weight: a per-(row, group)
+    scale commutes with the row permutations of llama_qkv / llama_gate_up."""
+    assert w16.dim() == 2 and group == Q4_GROUP, "the kernels of hip.gemv_q4 serve groups of 128"
+    n, k = w16.shape
+    assert k % group == 0, f"quant4_groups: K = {k} is no multiple of {group}"
+    wf = w16.detach().float().view(n, k // group, group)
+    amax = wf.abs().amax(dim=2)
+    scale = torch.where(amax > 0, amax / 7.0, torch.ones_like(amax))
+    u = (torch.clamp(torch.round(wf.double() / scale.double()[:, :, None]), -7.0, 7.0) + 8.0).to(torch.uint8).view(n, k // 8, 8)
+    qp = u[:, :, _Q4_LO] | (u[:, :, _Q4_HI] << 4)
+    return qp.reshape(n, k // 2).contiguous(), scale.contiguous()
+
+
+def dequant4_groups(qp, scale):
+    """the inverse of quant4_groups' nibble placement: (qp uint8 [N, K / 2], scale) -> (q int8 [N, K] in logical K order, |q| <= 7, scale unchanged);
+    the weight the format stands for is q.view(N, K / 128, 128) * scale[:, :, None]"""
+    n, kb = qp.shape
+    b = qp.view(n, kb // 4, 4)
+    u = torch.empty((n, kb // 4, 8), dtype=torch.uint8, device=qp.device)
+    u[:, :, _Q4_LO] = b & 15
+    u[:, :, _Q4_HI] = b >> 4
+    return (u.view(n, 2 * kb).to(torch.int16) - 8).to(torch.int8), scale
 
 
 def frag32(w):

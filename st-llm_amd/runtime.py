@@ -15,7 +15,9 @@
 
 Next to the numerics mode, the DECODE WEIGHT format (set_decode_weights): None — the one-token step streams the 16-bit weights the prefill uses
 (default) — or "int8": LlamaModel.decode_step runs its four projections per layer on the W8A16 kernels (hip.gemv_w8) over an int8 copy of the
-packed weights with one fp32 scale per output row.  Prefill, training, lm_head and attention are not affected.  STLLM_DECODE_WEIGHTS=int8 in the
+packed weights with one fp32 scale per output row — or "int4g128": the same four projections on the W4A16 kernels (hip.gemv_q4) over a 4-bit copy
+(pack.quant4_groups: two weights per byte, one fp32 scale per output row and group of 128 K elements; about 0.27 of the 16-bit bytes).  The name is the
+format's: a bare "int4" is refused.  Prefill, training, lm_head and attention are not affected.  STLLM_DECODE_WEIGHTS=int8 | int4g128 in the
 environment makes it the default of a process (the tools).
 """
 import contextlib
@@ -27,6 +29,7 @@ from .hip import torch_dtype
 
 _state = {"dtype": torch.bfloat16, "split": False, "vit": None}
 _decode = {"weights": None}
+DECODE_WEIGHTS = (None, "int8", "int4g128")
 SPLIT_NAMES = ("bf16x3", "split")
 MIXED_VIT = "fp16"   # the ViT's mode inside "mixed"
 
@@ -81,9 +84,9 @@ def use_dtype(d):
 
 
 def set_decode_weights(w):
-    """None | "int8" (see the module docstring)"""
-    if w not in (None, "int8"):
-        raise ValueError(f"decode weights: None or 'int8', got {w!r}")
+    """None | "int8" | "int4g128" (see the module docstring)"""
+    if w not in DECODE_WEIGHTS:
+        raise ValueError(f"decode weights: None, 'int8' or 'int4g128', got {w!r}")
     _decode["weights"] = w
 
 

@@ -12,7 +12,8 @@ ap.add_argument("--vit-depth", type=int, default=1)
 ap.add_argument("--qformer-layers", type=int, default=1)
 ap.add_argument("--tokens", type=int, default=16)
 ap.add_argument("--rows", type=int, default=1, help="sequences decoded together (5 = demo.py's beam search)")
-ap.add_argument("--weights", choices=["16", "int8"], default="16", help="decode weights: the 16-bit pack, or its int8 copy on the W8A16 kernels (runtime.set_decode_weights)")
+ap.add_argument("--weights", choices=["16", "int8", "int4g128"], default="16",
+                help="decode weights: the 16-bit pack, its int8 copy on the W8A16 kernels, or its 4-bit copy on the W4A16 kernels (runtime.set_decode_weights)")
 ap.add_argument("--gemv", type=int, default=-1, help="stllm_set_option('gemm_gemv'): -1 default (M <= 8), 1 = M <= 4, 0 off")
 ap.add_argument("--attn-single", type=int, default=1, help="stllm_set_option('attn_decode_single')")
 ap.add_argument("--ragged", default="", help="L1,L2,...: time ragged steps at these per-row cache lengths against uniform steps with every row at max(L), alternating")
@@ -30,7 +31,7 @@ lm = model.model
 S = 576
 from stllm_amd import hip
 from stllm_amd import runtime
-runtime.set_decode_weights("int8" if args.weights == "int8" else None)
+runtime.set_decode_weights(None if args.weights == "16" else args.weights)
 hip.set_option("gemm_gemv", args.gemv)
 hip.set_option("attn_decode_single", args.attn_single)
 
@@ -160,6 +161,8 @@ for _ in range(args.tokens):
     logits = model.logits_from(h, R, 1)
 torch.cuda.synchronize()
 ms = (time.perf_counter() - t0) / args.tokens * 1e3
-wbytes = sum(p.numel() for n, p in lm.named_parameters() if "layers" in n) * (1 if args.weights == "int8" and R <= 16 else 2) + 32000 * 4096 * 2
-wtag = ", weights int8" if args.weights == "int8" else ""
+# bytes per weight of the decoder layers: 2 | 1 (+ a scale per row: negligible) | 0.5 + one fp32 scale per 128 weights; more than 16 rows stream the 16-bit weights
+bpw = {"16": 2.0, "int8": 1.0, "int4g128": 0.5 + 4.0 / 128}[args.weights] if R <= 16 else 2.0
+wbytes = sum(p.numel() for n, p in lm.named_parameters() if "layers" in n) * bpw + 32000 * 4096 * 2
+wtag = "" if args.weights == "16" else f", weights {args.weights}"
 print(f"decode ({R} rows{wtag}, gemm_gemv {args.gemv}, attn_single {args.attn_single}, fuse_norm_rows {os.environ.get('STLLM_DECODE_FUSE_ROWS', '2')}): {ms:.2f} ms/step ({1e3 / ms:.1f} tok/s), weights streamed per token {wbytes / 1e9:.2f} GB => {wbytes / ms / 1e9:.2f} TB/s")
