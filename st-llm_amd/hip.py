@@ -580,22 +580,19 @@ def gemm(a, w, *, dtype, epilogue=EPI_STORE, bias=None, out=None, out_f32=False,
     return out
 
 
-def gemv_w8(a, wq, scale, *, dtype, epilogue=EPI_STORE, bias=None, resid=None, rope=None, rope_seq=0, rope_cols=0, out=None, out_f32=False,
-            a_norm=None, M=None, a_rows=None, o_rows=None):
-    """out = epilogue(scale * (a @ wq.T) + bias) for the decode regime (M <= 16): a [M,K] bf16 / fp16, wq int8 [N,K] (pack.quant8_rows of the
-    packed 16-bit weight), scale f32 [N] — stllm_gemv_w8 (stllm_hip.h).  Epilogues STORE / RESID / SWIGLU / ROPE as in gemm; a_norm=(x, gamma, eps)
-    with a=None: the fused RMSNorm operand (M <= 2).  A shape no int8 kernel covers raises (nothing else runs in its place)."""
+def _gemv_quant(name, args, wdtype, early, late, a, wq, scale, *, dtype, epilogue, bias, resid, rope, rope_seq, rope_cols, out, out_f32, a_norm, M, a_rows,
+                o_rows):
+    """what gemv_w8 and gemv_q4 share: the checks of the operands, `args` (a GemvW8Args / GemvQ4Args: same field names) filled in, the call of
+    stllm_<name>.  The format's own checks of (wq, scale) run where they always did: early(N) in front of the A operand, late(N, K) behind it."""
     td = torch_dtype(dtype)
     if td not in (torch.bfloat16, torch.float16):
-        raise RuntimeError(f"gemv_w8: 16-bit activations only, got {td}")
+        raise RuntimeError(f"{name}: 16-bit activations only, got {td}")
     if epilogue not in (EPI_STORE, EPI_RESID, EPI_SWIGLU, EPI_ROPE):
-        raise RuntimeError(f"gemv_w8: epilogue {epilogue} is not STORE / RESID / SWIGLU / ROPE")
-    args = GemvW8Args()
+        raise RuntimeError(f"{name}: epilogue {epilogue} is not STORE / RESID / SWIGLU / ROPE")
     args.dtype, args.epilogue, args.out_is_f32 = dtype_code(td), epilogue, int(out_f32)
-    _req(wq, torch.int8, "Wq"); _req(scale, torch.float32, "scale")
+    _req(wq, wdtype, "Wq"); _req(scale, torch.float32, "scale")
     N = wq.shape[0]
-    if scale.numel() != N or not scale.is_contiguous():
-        raise RuntimeError(f"gemv_w8: scale must be a contiguous f32 [{N}]")
+    early(N)
     if a_norm is not None:
         xn, gamma, eps = a_norm
         _req(xn, torch.float32, "a_norm x"); _req(gamma, torch.float32, "a_norm gamma")
@@ -608,12 +605,11 @@ def gemv_w8(a, wq, scale, *, dtype, epilogue=EPI_STORE, bias=None, resid=None, r
         if a_rows is not None:
             args.a_rows_per_batch, args.a_batch_stride = a_rows
             if M is None:
-                raise RuntimeError("gemv_w8: M is required with a_rows")
+                raise RuntimeError(f"{name}: M is required with a_rows")
         elif M is None:
             M = a.shape[0]
         args.A, args.lda = _p(a), a.stride(-2)
-    if wq.shape[1] != K:
-        raise RuntimeError(f"gemv_w8: Wq has {wq.shape[1]} columns, A has K = {K}")
+    late(N, K)
     args.Wq, args.ldw, args.scale = _p(wq), wq.stride(0), _p(scale)
     if bias is not None:
         _req(bias, torch.float32, "bias")
@@ -637,8 +633,24 @@ def gemv_w8(a, wq, scale, *, dtype, epilogue=EPI_STORE, bias=None, resid=None, r
         args.o_rows_per_batch, args.o_batch_stride = o_rows
     args.out, args.ldo = _p(out), out.stride(-2)
     args.M, args.N, args.K = M, N, K
-    _check(lib().stllm_gemv_w8(ctypes.byref(args), _stream()), "stllm_gemv_w8")
+    _check(getattr(lib(), "stllm_" + name)(ctypes.byref(args), _stream()), "stllm_" + name)
     return out
+
+
+def gemv_w8(a, wq, scale, *, dtype, epilogue=EPI_STORE, bias=None, resid=None, rope=None, rope_seq=0, rope_cols=0, out=None, out_f32=False,
+            a_norm=None, M=None, a_rows=None, o_rows=None):
+    """out = epilogue(scale * (a @ wq.T) + bias) for the decode regime (M <= 16): a [M,K] bf16 / fp16, wq int8 [N,K] (pack.quant8_rows of the
+    packed 16-bit weight), scale f32 [N] — stllm_gemv_w8 (stllm_hip.h).  Epilogues STORE / RESID / SWIGLU / ROPE as in gemm; a_norm=(x, gamma, eps)
+    with a=None: the fused RMSNorm operand (M <= 2).  A shape no int8 kernel covers raises (nothing else runs in its place)."""
+    def early(N):
+        if scale.numel() != N or not scale.is_contiguous():
+            raise RuntimeError(f"gemv_w8: scale must be a contiguous f32 [{N}]")
+
+    def late(N, K):
+        if wq.shape[1] != K:
+            raise RuntimeError(f"gemv_w8: Wq has {wq.shape[1]} columns, A has K = {K}")
+    return _gemv_quant("gemv_w8", GemvW8Args(), torch.int8, early, late, a, wq, scale, dtype=dtype, epilogue=epilogue, bias=bias, resid=resid, rope=rope,
+                       rope_seq=rope_seq, rope_cols=rope_cols, out=out, out_f32=out_f32, a_norm=a_norm, M=M, a_rows=a_rows, o_rows=o_rows)
 
 
 def gemv_q4(a, qp, scale, *, dtype, epilogue=EPI_STORE, bias=None, resid=None, rope=None, rope_seq=0, rope_cols=0, out=None, out_f32=False,
@@ -647,60 +659,16 @@ def gemv_q4(a, qp, scale, *, dtype, epilogue=EPI_STORE, bias=None, resid=None, r
     scale f32 [N,K/128]) = pack.quant4_groups of the packed 16-bit weight (q: pack.dequant4_groups) — stllm_gemv_q4 (stllm_hip.h).  The scale is applied
     per 128-element K group to the finished group sum, before bias / residual / SwiGLU / RoPE.  Epilogues, a_norm (M <= 2), a_rows / o_rows as in
     gemv_w8.  A shape no 4-bit kernel covers raises (nothing else runs in its place)."""
-    td = torch_dtype(dtype)
-    if td not in (torch.bfloat16, torch.float16):
-        raise RuntimeError(f"gemv_q4: 16-bit activations only, got {td}")
-    if epilogue not in (EPI_STORE, EPI_RESID, EPI_SWIGLU, EPI_ROPE):
-        raise RuntimeError(f"gemv_q4: epilogue {epilogue} is not STORE / RESID / SWIGLU / ROPE")
     args = GemvQ4Args()
-    args.dtype, args.epilogue, args.out_is_f32 = dtype_code(td), epilogue, int(out_f32)
-    _req(qp, torch.uint8, "Wq"); _req(scale, torch.float32, "scale")
-    N = qp.shape[0]
-    if a_norm is not None:
-        xn, gamma, eps = a_norm
-        _req(xn, torch.float32, "a_norm x"); _req(gamma, torch.float32, "a_norm gamma")
-        K = xn.shape[-1]
-        M = xn.shape[0] if M is None else M
-        args.a_norm_x, args.a_norm_ldx, args.a_norm_gamma, args.a_norm_eps = _p(xn), xn.stride(-2), _p(gamma), float(eps)
-    else:
-        _req(a, td, "A")
-        K = a.shape[-1]
-        if a_rows is not None:
-            args.a_rows_per_batch, args.a_batch_stride = a_rows
-            if M is None:
-                raise RuntimeError("gemv_q4: M is required with a_rows")
-        elif M is None:
-            M = a.shape[0]
-        args.A, args.lda = _p(a), a.stride(-2)
-    if qp.shape[1] * 2 != K:
-        raise RuntimeError(f"gemv_q4: Wq holds {qp.shape[1] * 2} weights per row, A has K = {K}")
-    if scale.dim() != 2 or tuple(scale.shape) != (N, -(-K // 128)):
-        raise RuntimeError(f"gemv_q4: scale must be f32 [{N}, {-(-K // 128)}]")
-    args.Wq, args.ldw, args.scale, args.ld_scale = _p(qp), qp.stride(0), _p(scale), scale.stride(0)
-    if bias is not None:
-        _req(bias, torch.float32, "bias")
-    args.bias = _p(bias)
-    if epilogue == EPI_RESID:
-        _req(resid, torch.float32, "resid")
-        out = resid if out is None else out
-        _req(out, torch.float32, "out")
-        args.resid, args.ldr = _p(resid), resid.stride(-2)
-    else:
-        n_out = N // 2 if epilogue == EPI_SWIGLU else N
-        odt = torch.float32 if (out_f32 and epilogue == EPI_STORE) else td
-        if out is None:
-            out = torch.empty((M, n_out), device=qp.device, dtype=odt)
-        _req(out, odt, "out")
-    if epilogue == EPI_ROPE:
-        cos, sin = rope
-        _req(cos, torch.float32, "rope cos"); _req(sin, torch.float32, "rope sin")
-        args.rope_cos, args.rope_sin, args.rope_seq, args.rope_cols = _p(cos), _p(sin), rope_seq, rope_cols
-    if o_rows is not None:
-        args.o_rows_per_batch, args.o_batch_stride = o_rows
-    args.out, args.ldo = _p(out), out.stride(-2)
-    args.M, args.N, args.K = M, N, K
-    _check(lib().stllm_gemv_q4(ctypes.byref(args), _stream()), "stllm_gemv_q4")
-    return out
+
+    def late(N, K):
+        if qp.shape[1] * 2 != K:
+            raise RuntimeError(f"gemv_q4: Wq holds {qp.shape[1] * 2} weights per row, A has K = {K}")
+        if scale.dim() != 2 or tuple(scale.shape) != (N, -(-K // 128)):
+            raise RuntimeError(f"gemv_q4: scale must be f32 [{N}, {-(-K // 128)}]")
+        args.ld_scale = scale.stride(0)
+    return _gemv_quant("gemv_q4", args, torch.uint8, lambda N: None, late, a, qp, scale, dtype=dtype, epilogue=epilogue, bias=bias, resid=resid, rope=rope,
+                       rope_seq=rope_seq, rope_cols=rope_cols, out=out, out_f32=out_f32, a_norm=a_norm, M=M, a_rows=a_rows, o_rows=o_rows)
 
 
 def stack_dtype_code(td, w):

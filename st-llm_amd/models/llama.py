@@ -8,7 +8,8 @@ Per layer:
     -> [o_proj GEMM + fp32 residual] -> RMSNorm -> [gate/up GEMM + SiLU(gate)*up epilogue]
     -> [down_proj GEMM + fp32 residual]
 
-then the final RMSNorm and lm_head on ALL positions (st_llm.py:122).
+then the final RMSNorm and lm_head on ALL positions (st_llm.py:122).  That sequence is written ONCE, in decoder_layer(); prefill, extend (plain and behind a
+shared base), the sequence-parallel halves and decode_step (16-bit, int8, int4, LoRA) call it with their own projection, QKV destination and attention.
 
 Decode with a KV cache (the step after the prefill in Chat.answer -> generate): the fused QKV
 buffer of every layer IS the cache — ``KVCache`` owns one [B, max_len, 3*D] buffer per layer; the prefill GEMM writes rows
@@ -17,14 +18,15 @@ rows [0, len] in place: no copies, no re-layout.  Decode reuses the prefill kern
 are future work.
 
 Int8 decode weights (runtime.set_decode_weights("int8")): decode_step streams an int8 copy of the four packed projection weights of every
-layer (pack.quant8_rows: one fp32 scale per output row) through the W8A16 kernels (hip.gemv_w8) — half the bytes per token.  The copy lives
+layer (pack.quant8_rows: one fp32 scale per output row) through the W8A16 kernels (hip.gemv_w8 behind decoder_layer's projection) — half the bytes per token.  The copy lives
 NEXT TO the 16-bit weights, which prefill / extend keep using: + 6.6 GB at 7B on top of the 13.5 GB of the 16-bit pack.  This is the
 reference's `device_8bit` knob (demo.py:41) with something behind it.
 
 Int4 decode weights (runtime.set_decode_weights("int4g128")): the same routing over a 4-bit copy (pack.quant4_groups: two weights per byte, one fp32 scale
 per output row and group of 128 K elements) on the W4A16 kernels (hip.gemv_q4) — about 0.27 of the 16-bit bytes per token, + 3.5 GB at 7B.  One quantised
-copy exists at a time: switching between "int8", "int4g128" and None frees the other at the next decode_step.
+copy exists at a time (one slot, LlamaModel._quant): switching between "int8", "int4g128" and None frees the other at the next decode_step.
 """
+import collections
 import os
 
 import torch
@@ -39,6 +41,43 @@ def _frag(pk, key):
     """keyword of hip.gemm for the fragment-major copy of pk[key], when the pack made one (pack.frag32_or_none)"""
     f = pk.get(key + "_frag")
     return {"w_frag": f} if f is not None else {}
+
+
+def gemm_proj(layers, dt, frag):
+    """decoder_layer's `proj` on the 16-bit packed weights: hip.gemm, with the fragment-major copy where the pack made one (prefill / extend: frag=True)"""
+    if frag:
+        return lambda li, key, a, **kw: hip.gemm(a, layers[li][key], dtype=dt, **kw, **_frag(layers[li], key))
+    return lambda li, key, a, **kw: hip.gemm(a, layers[li][key], dtype=dt, **kw)
+
+
+def decoder_layer(m, dt, x, pk, li, *, proj, qkv_to, attn, rope, rope_seq, fuse=False, part=None, qkv=None):
+    """THE decoder layer, on the fp32 residual x [M, D] in place:
+
+        norm 1 -> QKV projection + RoPE -> attention -> o_proj + residual -> norm 2 -> gate/up + SwiGLU -> down + residual
+
+    Every host path runs this body; they differ in three things only, which they pass in:
+      * the operand of the QKV projection: RMSNorm(x), with active adapters (`"lora_A" in pk`) m.qkv_operand's K-extended rows, or (fuse) no operand at
+        all — the norm rides inside the projection (a_norm=).  Norm 2 follows `fuse` as well; adapters never fuse norm 1.
+      * proj(li, key, a, **kw): the projection of a by layer li's weight `key` (hip.gemm / hip.gemv_w8 / hip.gemv_q4 behind it, looked up on `hip` when
+        called), and qkv_to(li): the keywords that say where the fused [q | k | v] rows land (none: a fresh tensor) — proj returns that destination;
+      * attn(li, qkv) -> the attention output rows that o_proj consumes.
+    m: the model, or a stand-in with `config` (and `qkv_operand` when adapters are active).  rope = (cos, sin) rows, row r of the projection at table
+    row r % rope_seq.  part: None = the whole layer; 0 = up to and including the QKV rows (returns their destination); 1 = from the attention on, over
+    `qkv` — the two halves sequence-parallel prefill interleaves its transfers with."""
+    eps, D = m.config.rms_norm_eps, m.config.hidden_size
+    if part != 1:
+        if "lora_A" in pk:
+            h, kw = m.qkv_operand(x, pk, dt), {}
+        else:
+            h, kw = (None, {"a_norm": (x, pk["ln1"], eps)}) if fuse else (hip.rmsnorm(x, pk["ln1"], eps, dtype=dt)[0], {})
+        qkv = proj(li, "wqkv", h, epilogue=hip.EPI_ROPE, rope=rope, rope_seq=rope_seq, rope_cols=2 * D, **kw, **qkv_to(li))
+        if part == 0:
+            return qkv
+    a = attn(li, qkv)
+    proj(li, "wo", a, epilogue=hip.EPI_RESID, resid=x)
+    h, kw = (None, {"a_norm": (x, pk["ln2"], eps)}) if fuse else (hip.rmsnorm(x, pk["ln2"], eps, dtype=dt)[0], {})
+    g = proj(li, "wgu", h, epilogue=hip.EPI_SWIGLU, **kw)
+    proj(li, "wdown", g, epilogue=hip.EPI_RESID, resid=x)
 
 
 class LlamaConfig:
@@ -198,6 +237,10 @@ class KVCache:
             self.len = n
 
 
+QuantCopy = collections.namedtuple("QuantCopy", "mode dt fingerprint layers")   # LlamaModel._quant: the one quantised copy of the packed weights
+# decode-weights mode -> (quantiser of a packed 16-bit weight, the hip function that multiplies by its result)
+QUANT = {"int8": (pack.quant8_rows, "gemv_w8"), "int4g128": (pack.quant4_groups, "gemv_q4")}
+QUANT_KEYS = ("wqkv", "wo", "wgu", "wdown")
 STACK_ENTRY = os.environ.get("STLLM_STACK_ENTRY", "1") != "0"   # 0: one C-ABI call per op instead of stllm_llama_layers / stllm_vit_blocks (A/B, tests)
 FUSE_NORM_ROWS = int(os.environ.get("STLLM_DECODE_FUSE_ROWS", "2"))   # decode steps with at most this many rows fuse RMSNorm into the GEMVs
 
@@ -212,8 +255,7 @@ class LlamaModel(nn.Module):
         self.layers = nn.ModuleList([LlamaDecoderLayer(config, device) for _ in range(config.num_hidden_layers)])
         self.norm = RMSNorm(config.hidden_size, config.rms_norm_eps, device)
         self._packed = {}
-        self._packed_w8 = {}   # dt -> (fingerprint, per-layer {wqkv, wo, wgu, wdown: (q int8, scale f32)}): the int8 decode weights, built on first use
-        self._packed_q4 = {}   # dt -> (fingerprint, per-layer {wqkv, wo, wgu, wdown: (qp uint8 [N, K/2], scale f32 [N, K/128])}): the 4-bit decode weights
+        self._quant = None   # QuantCopy | None: the quantised decode weights of ONE mode, per layer {wqkv, wo, wgu, wdown: (q, scale)}, built on first use
         self._rope = {}
         self._carr = {}   # C-side table of the packed layers (+ the cache it points into): rebuilt when either changes
         self._plist = ParamList(lambda: self.layers.parameters())
@@ -235,37 +277,29 @@ class LlamaModel(nn.Module):
             self._packed[dt] = hit
         return hit[1]
 
-    def pack_w8(self, dtype=None):
-        """the int8 decode weights: per layer {wqkv, wo, wgu, wdown} -> (q int8 [N, K], scale f32 [N]), quantised from the packed 16-bit weights
-        of pack(dt) (so the RoPE / gate-up row orders are inherited) and cached under the same parameter fingerprint (layers.params_fingerprint:
+    def pack_quant(self, mode, dtype=None):
+        """the quantised decode weights of `mode` (a key of QUANT): per layer {wqkv, wo, wgu, wdown} -> (q, scale), quantised from the packed 16-bit
+        weights of pack(dt) (so the RoPE / gate-up row orders are inherited) and cached under the same parameter fingerprint (layers.params_fingerprint:
         `_version` + `data_ptr()`): rebuilt, like the 16-bit pack, after an in-place edit of a master (p.copy_, p.mul_, an optimizer step through
         torch), load_state_dict or .to(device); a write through `p.data` or through a raw pointer bumps no version counter — such writers call
-        repack(), which drops both.  Also dropped when runtime.set_decode_weights(None) is seen by the next decode_step.  + 6.6 GB at 7B."""
+        repack(), which drops both.  ONE slot: building a copy drops the one of another mode or dtype; the first decode_step that sees another mode
+        (None included) drops it too."""
         dt = hip.torch_dtype(dtype) if dtype is not None else runtime.compute_dtype()
         layers = self.pack(dt)
         fp = self._packed[dt][0]
-        hit = self._packed_w8.get(dt)
-        if hit is None or hit[0] != fp:
-            self._packed_w8 = {}   # one copy at a time
-            self._packed_q4 = {}
-            hit = (fp, [{k: pack.quant8_rows(pk[k]) for k in ("wqkv", "wo", "wgu", "wdown")} for pk in layers])
-            self._packed_w8[dt] = hit
-        return hit[1]
+        if self._quant is None or self._quant[:3] != (mode, dt, fp):
+            self._quant = None   # free the old copy before the new one is built
+            quant = QUANT[mode][0]
+            self._quant = QuantCopy(mode, dt, fp, [{k: quant(pk[k]) for k in QUANT_KEYS} for pk in layers])
+        return self._quant.layers
+
+    def pack_w8(self, dtype=None):
+        """the int8 decode weights (pack_quant): (q int8 [N, K], scale f32 [N]) = pack.quant8_rows of every packed projection weight.  + 6.6 GB at 7B."""
+        return self.pack_quant("int8", dtype)
 
     def pack_q4(self, dtype=None):
-        """the 4-bit decode weights: per layer {wqkv, wo, wgu, wdown} -> (qp uint8 [N, K / 2], scale f32 [N, K / 128]) = pack.quant4_groups of the packed
-        16-bit weights of pack(dt); cached, rebuilt and dropped exactly as pack_w8's copy is (same fingerprint, repack(), state-dict loads, the mode
-        switched away from "int4g128").  Building it drops the int8 copy: one quantised copy at a time.  + 3.5 GB at 7B."""
-        dt = hip.torch_dtype(dtype) if dtype is not None else runtime.compute_dtype()
-        layers = self.pack(dt)
-        fp = self._packed[dt][0]
-        hit = self._packed_q4.get(dt)
-        if hit is None or hit[0] != fp:
-            self._packed_q4 = {}   # one copy at a time
-            self._packed_w8 = {}
-            hit = (fp, [{k: pack.quant4_groups(pk[k]) for k in ("wqkv", "wo", "wgu", "wdown")} for pk in layers])
-            self._packed_q4[dt] = hit
-        return hit[1]
+        """the 4-bit decode weights (pack_quant): (qp uint8 [N, K / 2], scale f32 [N, K / 128]) = pack.quant4_groups.  + 3.5 GB at 7B."""
+        return self.pack_quant("int4g128", dtype)
 
     def add_lora(self, r, lora_alpha=32):
         """peft's get_peft_model for target_modules = [q_proj, v_proj] (st_llm.py:165-177): fresh adapters (B = 0) on every decoder layer"""
@@ -287,18 +321,14 @@ class LlamaModel(nn.Module):
                 lora_mod.refresh_qkv(pk, *lora_mod.adapters_of(l), dt, self.config.num_attention_heads)
 
     def repack(self):
+        """drop every copy made from the parameters: the 16-bit pack, the quantised copy, the C-side table, the parameter list"""
         self._packed = {}
-        self._packed_w8 = {}
-        self._packed_q4 = {}
+        self._quant = None
         self._carr = {}
         self._plist.reset()
 
     def _load_from_state_dict(self, *a, **k):
-        self._packed = {}
-        self._packed_w8 = {}
-        self._packed_q4 = {}
-        self._carr = {}
-        self._plist.reset()
+        self.repack()
         return super()._load_from_state_dict(*a, **k)
 
     def rope(self, S, device):
@@ -368,27 +398,26 @@ class LlamaModel(nn.Module):
     def prefill_layers_per_op(self, x, layers, B, S, cos, sin, kv_len, cache, dt):
         """The decoder-layer loop as one C-ABI call per op — what stllm_llama_layers issues from C.  Kept as the reference the stack
         entry point is tested against (-m gpu: bit-identical) and as the body the test-only CPU contract backend runs."""
-        cfg = self.config
-        D = cfg.hidden_size
-        H = cfg.num_attention_heads
+        D, H = self.config.hidden_size, self.config.num_attention_heads
         hd = D // H
-        for li_, pk in enumerate(layers):
-            h = self.qkv_operand(x, pk, dt) if "lora_A" in pk else hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)[0]
-            if cache is None:
-                qkv = hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cos, sin), rope_seq=S, rope_cols=2 * D, **_frag(pk, "wqkv"))
-                strides = None
-            else:  # the cache buffer is the GEMM's output: rows (b, s) at b*max_len + s
-                qkv = cache.qkv[li_].view(B * cache.max_len, 3 * D)
-                hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cos, sin), rope_seq=S, rope_cols=2 * D,
-                         out=qkv, M=B * S, o_rows=(S, cache.max_len * 3 * D), **_frag(pk, "wqkv"))
-                strides = (cache.max_len * 3 * D, 3 * D)
-            a = hip.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B=B, H=H, Sq=S, Skv=S, D=hd,
-                              scale=hd ** -0.5, causal=True, kv_len=kv_len, q_strides=strides, k_strides=strides,
-                              v_strides=strides)
-            hip.gemm(a, pk["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
-            h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
-            g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, **_frag(pk, "wgu"))
-            hip.gemm(g, pk["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
+        if cache is None:
+            strides = None
+
+            def qkv_to(li):
+                return {}
+        else:  # the cache buffer is the GEMM's output: rows (b, s) at b*max_len + s
+            strides = (cache.max_len * 3 * D, 3 * D)
+
+            def qkv_to(li):
+                return dict(out=cache.qkv[li].view(B * cache.max_len, 3 * D), M=B * S, o_rows=(S, cache.max_len * 3 * D))
+
+        def attn(li, qkv):
+            return hip.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B=B, H=H, Sq=S, Skv=S, D=hd,
+                                 scale=hd ** -0.5, causal=True, kv_len=kv_len, q_strides=strides, k_strides=strides,
+                                 v_strides=strides)
+        proj = gemm_proj(layers, dt, True)
+        for li, pk in enumerate(layers):
+            decoder_layer(self, dt, x, pk, li, proj=proj, qkv_to=qkv_to, attn=attn, rope=(cos, sin), rope_seq=S)
         return x
 
     def extend(self, inputs_embeds, cache, lengths=None):
@@ -414,30 +443,21 @@ class LlamaModel(nn.Module):
             assert len(lengths) == B and all(1 <= n <= S for n in lengths)
             if len(set(lengths)) == 1 and lengths[0] == S:
                 lengths = None
-        if cache.base is not None:   # a shared base: the per-op body on hip.attention_shared (the one-call C stack entry does not know about bases)
-            layers = self.pack(dt)
-            x = inputs_embeds.reshape(B * S, D).float().clone()
-            cos, sin = self.rope(cache.max_len, inputs_embeds.device)
-            self.extend_layers_shared(x, layers, B, S, P, cos[P:P + S], sin[P:P + S], cache, dt, lengths)
-            cache.len = P + S
-            if lengths is not None:
-                cache.set_lens([P + n for n in lengths])
-            h16, h32 = hip.rmsnorm(x, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
-            return h32.view(B, S, D), h16
-        if P == 0:
+        if P == 0:   # (a cache with a base holds P > 0 positions)
             mask = None if lengths is None else (torch.arange(S)[None, :] < torch.tensor(lengths)[:, None]).long()
             return self.prefill(inputs_embeds, mask, cache=cache)
         layers = self.pack(dt)
-        H = cfg.num_attention_heads
         x = inputs_embeds.reshape(B * S, D).float().clone()
         cos, sin = self.rope(cache.max_len, inputs_embeds.device)
         cos, sin = cos[P:P + S], sin[P:P + S]
-        if lengths is not None:
+        if cache.base is not None:   # a shared base: the per-op body on hip.attention_shared (the one-call C stack entry does not know about bases)
+            self.extend_layers_shared(x, layers, B, S, P, cos, sin, cache, dt, lengths)
+        elif lengths is not None:
             kv_len = hip.h2d(torch.tensor([P + n for n in lengths], dtype=torch.int32), inputs_embeds.device)
             self.extend_layers_per_op(x, layers, B, S, P, cos, sin, cache, dt, kv_len=kv_len)
         elif STACK_ENTRY and "lora_A" not in layers[0]:
-            hip.llama_layers_extend(x, layers, hip.llama_layer_array(layers, cache), B=B, S=S, pos0=P, n_heads=H, eps=cfg.rms_norm_eps, rope=(cos, sin),
-                                    dtype=dt, cache=cache)
+            hip.llama_layers_extend(x, layers, hip.llama_layer_array(layers, cache), B=B, S=S, pos0=P, n_heads=cfg.num_attention_heads, eps=cfg.rms_norm_eps,
+                                    rope=(cos, sin), dtype=dt, cache=cache)
         else:
             self.extend_layers_per_op(x, layers, B, S, P, cos, sin, cache, dt)
         cache.len = P + S
@@ -449,23 +469,21 @@ class LlamaModel(nn.Module):
     def extend_layers_per_op(self, x, layers, B, S, P, cos, sin, cache, dt, kv_len=None):
         """extend's layer loop as one C-ABI call per op — what stllm_llama_layers_extend issues from C (bit-identical), the body active LoRA adapters
         run, and the one the test-only CPU contract backend runs"""
-        cfg = self.config
-        D = cfg.hidden_size
-        H = cfg.num_attention_heads
+        D, H = self.config.hidden_size, self.config.num_attention_heads
         hd = D // H
         ML3 = cache.max_len * 3 * D
-        for li_, pk in enumerate(layers):
-            h = self.qkv_operand(x, pk, dt) if "lora_A" in pk else hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)[0]
-            full = cache.qkv[li_].view(B * cache.max_len, 3 * D)
-            new = full[P:]                                         # row (b, s) of the suffix at b * max_len + P + s
-            hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cos, sin), rope_seq=S, rope_cols=2 * D,
-                     out=new, M=B * S, o_rows=(S, ML3), **_frag(pk, "wqkv"))
-            a = hip.attention(new[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=S, Skv=P + S, D=hd, scale=hd ** -0.5, causal=True,
-                              q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D), v_strides=(ML3, 3 * D), q_off=P, **({"kv_len": kv_len} if kv_len is not None else {}))
-            hip.gemm(a, pk["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
-            h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
-            g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, **_frag(pk, "wgu"))
-            hip.gemm(g, pk["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
+        kv = {"kv_len": kv_len} if kv_len is not None else {}
+
+        def qkv_to(li):   # row (b, s) of the suffix at b * max_len + P + s
+            return dict(out=cache.qkv[li].view(B * cache.max_len, 3 * D)[P:], M=B * S, o_rows=(S, ML3))
+
+        def attn(li, new):
+            full = cache.qkv[li].view(B * cache.max_len, 3 * D)
+            return hip.attention(new[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=S, Skv=P + S, D=hd, scale=hd ** -0.5, causal=True,
+                                 q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D), v_strides=(ML3, 3 * D), q_off=P, **kv)
+        proj = gemm_proj(layers, dt, True)
+        for li, pk in enumerate(layers):
+            decoder_layer(self, dt, x, pk, li, proj=proj, qkv_to=qkv_to, attn=attn, rope=(cos, sin), rope_seq=S)
         return x
 
     def extend_layers_shared(self, x, layers, B, S, pos, cos, sin, cache, dt, lengths=None):
@@ -473,9 +491,7 @@ class LlamaModel(nn.Module):
         of the cache's own buffers.  The QKV GEMM writes a dense [B * S, 3D] buffer — the 16-bit kernels behind hip.attention_shared walk the R * S query
         rows of a group at ONE row stride — whose rows are then copied into the cache; the attention reads the base's P keys once per group and row b's own
         off + S_b suffix keys (causal with the query offset `off`)."""
-        cfg = self.config
-        D = cfg.hidden_size
-        H = cfg.num_attention_heads
+        D, H = self.config.hidden_size, self.config.num_attention_heads
         hd = D // H
         base, P = cache.base, cache.base_len
         off = pos - P
@@ -483,19 +499,17 @@ class LlamaModel(nn.Module):
         dev = x.device
         sfx_len = None if lengths is None else hip.h2d(torch.tensor([off + n for n in lengths], dtype=torch.int32), dev)
         dense = torch.empty((B * S, 3 * D), device=dev, dtype=dt)
-        for li_, pk in enumerate(layers):
-            h = self.qkv_operand(x, pk, dt) if "lora_A" in pk else hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)[0]
-            hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cos, sin), rope_seq=S, rope_cols=2 * D, out=dense, **_frag(pk, "wqkv"))
-            cache.qkv[li_][:, off:off + S].copy_(dense.view(B, S, 3 * D))
-            bq = base.qkv[li_].view(base.batch * base.max_len, 3 * D)
-            sq = cache.qkv[li_].view(B * cap, 3 * D)
-            a = hip.attention_shared(dense[:, :D], bq[:, D:2 * D], bq[:, 2 * D:], sq[:, D:2 * D], sq[:, 2 * D:], B=B, G=base.batch, H=H, Sq=S, P=P, D=hd,
-                                     scale=hd ** -0.5, max_sfx=off + S, sfx_len=sfx_len, sfx_q_off=off, causal=True, q_strides=(S * 3 * D, 3 * D),
-                                     kp_strides=(base.max_len * 3 * D, 3 * D), ks_strides=(cap * 3 * D, 3 * D))
-            hip.gemm(a, pk["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
-            h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
-            g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, **_frag(pk, "wgu"))
-            hip.gemm(g, pk["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
+
+        def attn(li, dense):
+            cache.qkv[li][:, off:off + S].copy_(dense.view(B, S, 3 * D))
+            bq = base.qkv[li].view(base.batch * base.max_len, 3 * D)
+            sq = cache.qkv[li].view(B * cap, 3 * D)
+            return hip.attention_shared(dense[:, :D], bq[:, D:2 * D], bq[:, 2 * D:], sq[:, D:2 * D], sq[:, 2 * D:], B=B, G=base.batch, H=H, Sq=S, P=P, D=hd,
+                                        scale=hd ** -0.5, max_sfx=off + S, sfx_len=sfx_len, sfx_q_off=off, causal=True, q_strides=(S * 3 * D, 3 * D),
+                                        kp_strides=(base.max_len * 3 * D, 3 * D), ks_strides=(cap * 3 * D, 3 * D))
+        proj = gemm_proj(layers, dt, True)
+        for li, pk in enumerate(layers):
+            decoder_layer(self, dt, x, pk, li, proj=proj, qkv_to=lambda li: {"out": dense}, attn=attn, rope=(cos, sin), rope_seq=S)
         return x
 
     def qkv_operand(self, x, pk, dt):
@@ -518,15 +532,11 @@ class LlamaModel(nn.Module):
         if carr is not None:
             return hip.llama_layer_sp(x, carr, li, qkv, s0=s0, s1=s1, part=part, n_heads=H, eps=cfg.rms_norm_eps, rope=(cos_l, sin_l), dtype=dt,
                                       inter=pk["wgu"].shape[0] // 2)
-        if part == 0:
-            h, _ = hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)
-            hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cos_l, sin_l), rope_seq=s1 - s0, rope_cols=2 * D, out=qkv[s0:s1], **_frag(pk, "wqkv"))
-            return x
-        a = hip.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B=1, H=H, Sq=s1, Skv=s1, D=hd, scale=hd ** -0.5, causal=True)
-        hip.gemm(a[s0:s1], pk["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
-        h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
-        g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, **_frag(pk, "wgu"))
-        hip.gemm(g, pk["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
+
+        def attn(li, qkv):   # over all s1 rows; o_proj takes this rank's
+            return hip.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B=1, H=H, Sq=s1, Skv=s1, D=hd, scale=hd ** -0.5, causal=True)[s0:s1]
+        decoder_layer(self, dt, x, pk, li, proj=gemm_proj(layers, dt, True), qkv_to=lambda li: {"out": qkv[s0:s1]}, attn=attn, rope=(cos_l, sin_l),
+                      rope_seq=s1 - s0, part=part, qkv=qkv)
         return x
 
     def prefill_sp(self, inputs_embeds, sp):
@@ -603,89 +613,64 @@ class LlamaModel(nn.Module):
             raise NotImplementedError("decode_step on a KV cache with a shared base runs in the bf16 / fp16 / fp32 modes; fork() it for bf16x3 / mixed")
         layers = self.pack(dt)
         B, _, D = x_new.shape
-        w8 = q4 = None
+        qw = None
         if wmode is not None:
             if "lora_A" in layers[0]:
                 raise NotImplementedError(f"{wmode} decode weights with active LoRA adapters: merge_adapter() first")
             if B <= 16:   # the decode regime of hip.gemv_w8 / hip.gemv_q4; larger batches stream the 16-bit weights on the tile kernels
-                if wmode == "int8":
-                    w8 = self.pack_w8(dt)
-                else:
-                    q4 = self.pack_q4(dt)
-        if wmode != "int8" and self._packed_w8:
-            self._packed_w8 = {}   # the mode was switched away: free the int8 copy
-        if wmode != "int4g128" and self._packed_q4:
-            self._packed_q4 = {}   # likewise the 4-bit copy
-        H = cfg.num_attention_heads
-        hd = D // H
+                qw = self.pack_quant(wmode, dt)
+        if self._quant is not None and self._quant.mode != wmode:
+            self._quant = None   # the mode was switched away: free the quantised copy
         pos = cache.len
         assert pos < cache.max_len, "KV cache full"
         cos, sin = self.rope(cache.max_len, x_new.device)
         cpos, spos = cos[pos:pos + 1], sin[pos:pos + 1]
         rs, rg = 1, None
-        if cache.base is not None:
-            # a shared base: ALWAYS the scratch-row route of the ragged step (one path for uniform and ragged suffixes) — RoPE at the total positions, the
-            # [k | v] columns appended at the LOCAL position lens[b] - P of the cache's own buffers, attention through hip.attention_shared (decode_attn)
+        if cache.base is not None or cache.lens is not None:
+            # ragged step: token b sits at position lens[b].  The RoPE epilogues take pos = row % rope_seq, so B table rows cos[lens[b]] with rope_seq = B
+            # need no GEMV change; the positions / lengths travel through the pinned ring (the host knows them: no device synchronisation).  The QKV
+            # GEMV writes rows at ONE stride only -> a dense [B, 3D] scratch row, scattered into the cache by kv_append_rows (decode_attn).
+            # A shared base ALWAYS takes this route (one path for uniform and ragged suffixes): RoPE at the total positions, the [k | v] columns appended
+            # at the LOCAL position lens[b] - P of the cache's own buffers, attention through hip.attention_shared (decode_attn)
             dev = x_new.device
             assert cache.batch == B
-            lens_, P_ = (cache.lens if cache.lens is not None else [pos] * B), cache.base_len
+            lens_, P_ = cache.lens or [pos] * B, cache.base_len
             pos_d = hip.h2d(torch.tensor(lens_, dtype=torch.int32), dev)
             cpos, spos = hip.gather_rows(cos, pos_d), hip.gather_rows(sin, pos_d)
             rs = B
-            rg = dict(pos=hip.h2d(torch.tensor([n - P_ for n in lens_], dtype=torch.int32), dev),
+            # without a base the local positions ARE the total ones: the table just uploaded serves as both
+            rg = dict(pos=pos_d if cache.base is None else hip.h2d(torch.tensor([n - P_ for n in lens_], dtype=torch.int32), dev),
                       kv_len=hip.h2d(torch.tensor([n - P_ + 1 for n in lens_], dtype=torch.int32), dev), max_kv=pos - P_ + 1,
                       scratch=torch.empty((B, 3 * D), device=dev, dtype=dt))
-        elif cache.lens is not None:
-            # ragged step: token b sits at position lens[b].  The RoPE epilogues take pos = row % rope_seq, so B table rows cos[lens[b]] with rope_seq = B
-            # need no GEMV change; the positions / lengths travel through the pinned ring (the host knows them: no device synchronisation).  The QKV
-            # GEMV writes rows at ONE stride only -> a dense [B, 3D] scratch row, scattered into the cache by kv_append_rows (decode_attn)
-            dev = x_new.device
-            assert cache.batch == B
-            pos_d = hip.h2d(torch.tensor(cache.lens, dtype=torch.int32), dev)
-            cpos, spos = hip.gather_rows(cos, pos_d), hip.gather_rows(sin, pos_d)
-            rs = B
-            rg = dict(pos=pos_d, kv_len=hip.h2d(torch.tensor([n + 1 for n in cache.lens], dtype=torch.int32), dev), max_kv=pos + 1,
-                      scratch=torch.empty((B, 3 * D), device=dev, dtype=dt))
         x = x_new.reshape(B, D).float().clone()
-        ML3 = cache.max_len * 3 * D
         # 16-bit modes, <= 8 rows: both RMSNorms ride inside the GEMV that consumes them (2 launches per layer fewer)
         # (every workgroup of the GEMV recomputes the norm of all its rows: worth it for 1-2 rows — 3.70 -> 3.29 ms/token —, a loss for
         #  the 5 rows of beam search, where 2752 workgroups x 6 staged rows re-read 0.5 GB through L2)
         fuse = dt != torch.float32 and B <= FUSE_NORM_ROWS
-        for li_, pk in enumerate(layers):
-            row = cache.qkv[li_][:, pos] if rg is None else rg["scratch"]   # [B, 3D]: a view of the cache, row stride max_len*3D | the dense scratch
-            if w8 is not None:   # the same step over the int8 weights (W8A16 kernels): same epilogues, same fused norms
-                self.decode_layer_w8(x, pk, w8[li_], row, cache, li_, pos, cpos, spos, fuse and B <= 2, dt, rope_seq=rs, rg=rg)   # (stllm_gemv_w8 fuses the norm for <= 2 rows)
-                continue
-            if q4 is not None:   # likewise over the 4-bit weights (W4A16 kernels)
-                self.decode_layer_q4(x, pk, q4[li_], row, cache, li_, pos, cpos, spos, fuse and B <= 2, dt, rope_seq=rs, rg=rg)   # (stllm_gemv_q4 fuses the norm for <= 2 rows)
-                continue
-            if "lora_A" in pk:   # active adapters: the fused-RMSNorm GEMV cannot see t = h A^T — norm, down projection, then the GEMV over K = D + P
-                hip.gemm(self.qkv_operand(x, pk, dt), pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rs, rope_cols=2 * D, out=row)
-            elif fuse:
-                hip.gemm(None, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rs, rope_cols=2 * D, out=row,
-                         a_norm=(x, pk["ln1"], cfg.rms_norm_eps))
-            else:
-                h, _ = hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)
-                hip.gemm(h, pk["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rs, rope_cols=2 * D, out=row)
-            a = self.decode_attn(row, cache, li_, pos, rg)
-            hip.gemm(a, pk["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
-            if fuse:
-                g = hip.gemm(None, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, a_norm=(x, pk["ln2"], cfg.rms_norm_eps))
-            else:
-                h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
-                g = hip.gemm(h, pk["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU)
-            hip.gemm(g, pk["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
-        if rg is None or cache.lens is None:
-            cache.len = pos + 1
-        else:
+        if qw is None:
+            proj = gemm_proj(layers, dt, False)
+        else:   # the same step over the quantised weights (W8A16 / W4A16 kernels): same epilogues, same fused norms
+            fuse = fuse and B <= 2   # (stllm_gemv_w8 / stllm_gemv_q4 fuse the norm for <= 2 rows)
+            fn = QUANT[wmode][1]
+
+            def proj(li, key, a, **kw):
+                return getattr(hip, fn)(a, *qw[li][key], dtype=dt, **kw)
+
+        def qkv_to(li):   # [B, 3D]: row `pos` of the layer's cache buffer, a view with the row stride max_len*3D | the dense scratch
+            return {"out": cache.qkv[li][:, pos] if rg is None else rg["scratch"]}
+
+        def attn(li, row):
+            return self.decode_attn(row, cache, li, pos, rg)
+        for li, pk in enumerate(layers):
+            decoder_layer(self, dt, x, pk, li, proj=proj, qkv_to=qkv_to, attn=attn, rope=(cpos, spos), rope_seq=rs, fuse=fuse)
+        if cache.lens is not None:
             cache.lens = [n + 1 for n in cache.lens]
-            cache.len = pos + 1
+        cache.len = pos + 1
         h16, h32 = hip.rmsnorm(x, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
         return h32.view(B, 1, D), h16
 
     def decode_attn(self, row, cache, li_, pos, rg=None):
-        """the attention half of one decode layer, shared by the 16-bit, int8-weight and LoRA steps.  row: the new tokens' fused [q | k | v] rows [B, 3D].
+        """the attention half of one decode layer, shared by the 16-bit, quantised-weight and LoRA steps (decode_step's `attn`).  row: the new tokens' fused [q | k | v] rows [B, 3D].
         Uniform (rg None): row IS row `pos` of the layer's cache buffer, every batch row attends keys [0, pos].  Ragged (rg: decode_step's per-step
         tables): row is the dense scratch — its [k | v] columns are scattered to position lens[b] of every cache row (one launch, kv_append_rows), then
         q is read from the scratch and row b attends its own lens[b] + 1 cached keys (the ragged decode kernels; fp32: stllm_attention's kv_len)."""
@@ -717,33 +702,6 @@ class LlamaModel(nn.Module):
         return hip.attention(row[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=1, Skv=rg["max_kv"], D=hd,
                              scale=hd ** -0.5, causal=False, kv_len=rg["kv_len"], q_strides=(3 * D, 3 * D), k_strides=(ML3, 3 * D),
                              v_strides=(ML3, 3 * D))
-
-    def decode_layer_w8(self, x, pk, q8, row, cache, li_, pos, cpos, spos, fuse, dt, rope_seq=1, rg=None):
-        """one decoder layer of decode_step with its four projections on hip.gemv_w8 (q8: pack_w8's entry of the layer); attention and norms as in the 16-bit step"""
-        self.decode_layer_quant(hip.gemv_w8, x, pk, q8, row, cache, li_, pos, cpos, spos, fuse, dt, rope_seq, rg)
-
-    def decode_layer_q4(self, x, pk, q4, row, cache, li_, pos, cpos, spos, fuse, dt, rope_seq=1, rg=None):
-        """the same layer on hip.gemv_q4 (q4: pack_q4's entry of the layer)"""
-        self.decode_layer_quant(hip.gemv_q4, x, pk, q4, row, cache, li_, pos, cpos, spos, fuse, dt, rope_seq, rg)
-
-    def decode_layer_quant(self, gemv, x, pk, qw, row, cache, li_, pos, cpos, spos, fuse, dt, rope_seq, rg):
-        """the shared body: gemv(a, q, scale, ...) is hip.gemv_w8 or hip.gemv_q4 (one signature), qw the layer's {name: (q, scale)}"""
-        cfg = self.config
-        B, D = x.shape
-        if fuse:
-            gemv(None, *qw["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rope_seq, rope_cols=2 * D, out=row,
-                 a_norm=(x, pk["ln1"], cfg.rms_norm_eps))
-        else:
-            h, _ = hip.rmsnorm(x, pk["ln1"], cfg.rms_norm_eps, dtype=dt)
-            gemv(h, *qw["wqkv"], dtype=dt, epilogue=hip.EPI_ROPE, rope=(cpos, spos), rope_seq=rope_seq, rope_cols=2 * D, out=row)
-        a = self.decode_attn(row, cache, li_, pos, rg)
-        gemv(a, *qw["wo"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
-        if fuse:
-            g = gemv(None, *qw["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU, a_norm=(x, pk["ln2"], cfg.rms_norm_eps))
-        else:
-            h, _ = hip.rmsnorm(x, pk["ln2"], cfg.rms_norm_eps, dtype=dt)
-            g = gemv(h, *qw["wgu"], dtype=dt, epilogue=hip.EPI_SWIGLU)
-        gemv(g, *qw["wdown"], dtype=dt, epilogue=hip.EPI_RESID, resid=x)
 
     def new_cache(self, batch, max_len, device):
         return KVCache(len(self.layers), batch, max_len, self.config.hidden_size, runtime.compute_dtype(), device)

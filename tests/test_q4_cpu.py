@@ -287,31 +287,33 @@ def test_int4_weight_cache_follows_the_parameters_and_the_mode(small):
             runtime.set_decode_weights("int4g128")
             assert runtime.decode_weights() == "int4g128"
             a = _decode_run(small, emb, 4, 2)
-            first = lm._packed_q4[torch.bfloat16][1]
+            assert lm._quant[:2] == ("int4g128", torch.bfloat16)
+            first = lm._quant.layers
             assert set(first[0]) == set(Q4_KEYS) and first[1]["wdown"][0].dtype == torch.uint8
             assert first[1]["wdown"][0].shape == (256, 384) and first[1]["wdown"][1].shape == (256, 6) and first[0]["wqkv"][1].shape == (768, 2)
             _decode_run(small, emb, 4, 1)
-            assert lm._packed_q4[torch.bfloat16][1] is first, "unchanged parameters: the cached copy"
+            assert lm._quant[:2] == ("int4g128", torch.bfloat16) and lm._quant.layers is first, "unchanged parameters: the cached copy"
             w.copy_(w0 * 1.5)
             b = _decode_run(small, emb, 4, 2)
-            second = lm._packed_q4[torch.bfloat16][1]
+            assert lm._quant[:2] == ("int4g128", torch.bfloat16)
+            second = lm._quant.layers
             assert second is not first and not torch.equal(second[1]["wdown"][1], first[1]["wdown"][1])
             assert torch.equal(second[0]["wqkv"][0], first[0]["wqkv"][0]) and not torch.equal(a[-1], b[-1])
-            assert lm._packed_w8 == {}
+            assert lm._quant.mode != "int8", "no int8 copy is held"
             runtime.set_decode_weights("int8")
             CB.CALLS.clear(); CB8.CALLS.clear()
             _decode_run(small, emb, 4, 1)
-            assert lm._packed_q4 == {} and torch.bfloat16 in lm._packed_w8 and CB.CALLS == [] and len(CB8.CALLS) == 8, "int8: the 4-bit copy is freed"
+            assert lm._quant[:2] == ("int8", torch.bfloat16) and CB.CALLS == [] and len(CB8.CALLS) == 8, "int8: the 4-bit copy is freed"
             runtime.set_decode_weights("int4g128")
             CB8.CALLS.clear()
             _decode_run(small, emb, 4, 1)
-            assert lm._packed_w8 == {} and torch.bfloat16 in lm._packed_q4 and len(CB.CALLS) == 8 and CB8.CALLS == [], "and back: the int8 copy is freed"
+            assert lm._quant[:2] == ("int4g128", torch.bfloat16) and len(CB.CALLS) == 8 and CB8.CALLS == [], "and back: the int8 copy is freed"
             lm.repack()
-            assert lm._packed_q4 == {}
+            assert lm._quant is None
             _decode_run(small, emb, 4, 1)
             runtime.set_decode_weights(None)
             _decode_run(small, emb, 4, 1)
-            assert lm._packed_q4 == {} and lm._packed_w8 == {}, "mode off: no quantised copy"
+            assert lm._quant is None, "mode off: no quantised copy"
             for bad in ("int4", "int4g64", "q4"):
                 with pytest.raises(ValueError, match="int4g128"):
                     runtime.set_decode_weights(bad)

@@ -159,7 +159,7 @@ def test_q4_generate_paths(hip, gen_model, path):
                 got = run()
             kernels = list(seen)
             again = run()
-        assert len(seen) == len(kernels) and model.model._packed_q4 == {}, "mode off again: no launch, the 4-bit copy freed by the next decode step"
+        assert len(seen) == len(kernels) and model.model._quant is None, "mode off again: no launch, the 4-bit copy freed by the next decode step"
     assert len(kernels) > 0 and len(kernels) % 8 == 0, len(kernels)           # 2 layers x 4 projections per decode step
     fam = "gemv_q4_mfma_kernel<f16_t" if path in ("5 beams", "share_prefix") else "gemv_q4_kernel<f16_t"
     assert all(k.startswith(fam) for k in kernels), (path, sorted(set(kernels)))

@@ -275,18 +275,20 @@ def test_int8_weight_cache_follows_the_parameters_and_the_mode(small):
             runtime.set_decode_weights("int8")
             assert runtime.decode_weights() == "int8"
             a = _decode_run(small, emb, 4, 2)
-            first = lm._packed_w8[torch.bfloat16][1]
+            assert lm._quant[:2] == ("int8", torch.bfloat16)
+            first = lm._quant.layers
             assert set(first[0]) == set(W8_KEYS) and first[1]["wdown"][0].dtype == torch.int8 and first[1]["wdown"][1].shape == (256,)
             _decode_run(small, emb, 4, 1)
-            assert lm._packed_w8[torch.bfloat16][1] is first, "unchanged parameters: the cached copy"
+            assert lm._quant[:2] == ("int8", torch.bfloat16) and lm._quant.layers is first, "unchanged parameters: the cached copy"
             w.copy_(w0 * 1.5)
             b = _decode_run(small, emb, 4, 2)
-            second = lm._packed_w8[torch.bfloat16][1]
+            assert lm._quant[:2] == ("int8", torch.bfloat16)
+            second = lm._quant.layers
             assert second is not first and not torch.equal(second[1]["wdown"][1], first[1]["wdown"][1])
             assert torch.equal(second[0]["wqkv"][0], first[0]["wqkv"][0]) and not torch.equal(a[-1], b[-1])
             runtime.set_decode_weights(None)
             _decode_run(small, emb, 4, 1)
-            assert lm._packed_w8 == {}, "mode off: the int8 copy is freed"
+            assert lm._quant is None, "mode off: the int8 copy is freed"
             with pytest.raises(ValueError):
                 runtime.set_decode_weights("int4")
     finally:

@@ -177,7 +177,7 @@ def test_w8_generate_paths(hip):
         print(f"w8 generate [{name}]: {len(kernels)} gemv_w8 launches, ids {ids.flatten().tolist()}")
     assert on[0][0].shape == (1, 6) and on[3][0].shape[0] == 3 and on[4][0].shape[0] == 1
     assert all(k == [] for _, k in before) and all(k == [] for _, k in after), "mode off: no int8 launch"
-    assert model.model._packed_w8 == {}, "mode off: the int8 copy is freed by the next decode step"
+    assert model.model._quant is None, "mode off: the int8 copy is freed by the next decode step"
     assert all(torch.equal(a[0], b[0]) for a, b in zip(before, after)), "mode off again: the ids of the run before it was switched on"
 
 
