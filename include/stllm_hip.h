@@ -54,6 +54,24 @@ typedef enum {
 
 typedef enum { STLLM_ACT_NONE = 0, STLLM_ACT_GELU = 1, STLLM_ACT_RELU = 2 } stllm_act;
 
+/*
+ * MEMORY REGIONS — what every entry point below promises about the bytes it touches (tests/test_poison_*.py and the NaN / guard cases of the kernel
+ * tests hold the library to it; every buffer a caller passes may come straight from an allocator that does not clear memory):
+ *   never read        an operand given as rows with a leading dimension, [rows, ld], is read at the columns [0, width) of its LOGICAL rows only:
+ *                     never the columns [width, ld), never a row in front of, between (2-level rows: only row (m / rows_per_batch, m % rows_per_batch))
+ *                     or behind the logical rows, never a row at or behind a length bound (Skv, kv_len[b], sfx_len[b], P) unless the entry point's own
+ *                     paragraph lists it under "read, weightless".  NaN or any other bit pattern there cannot reach an output.  A tile that overhangs
+ *                     M re-reads the LAST logical row instead of the row behind it.
+ *   read, weightless  loaded, but multiplied by an exact zero weight or masked: the VALUE cannot matter provided it is FINITE (0 x NaN = NaN).  The caller
+ *                     must have written something finite there.  Only stllm_attention / stllm_attention_offset have such a region (their paragraphs).
+ *   never written     an output [rows, ldo] is written at the columns [0, width) of its logical rows and NOWHERE else: not the columns [width, ldo), not
+ *                     a row in front of / between / behind them, not a row whose index is >= M inside an overhanging tile.  Inputs are never written
+ *                     (RESID in place writes `resid` as its output).  Every logical output element IS written (no "left as it was"), except where a
+ *                     paragraph says so (free slots of stllm_kv_append_rows).
+ *   workspace         "no initialisation needed" means exactly that: every byte that is read was written earlier in the same call.  The contents after
+ *                     the call are undefined.  The one exception is stllm_gemm_args.workspace (flags: zero at allocation, kept consistent by the kernels).
+ * Entry points without a paragraph of their own (the element-wise, gather and training ops) follow the three rules with no exception.
+ */
 const char* stllm_last_error(void);
 int stllm_abi_version(void);
 /* HOST utility (no GPU involved): n values of the deterministic synthetic-weight stream (stllm_amd/synth.py: random-init benchmarks,
@@ -84,6 +102,12 @@ const char* stllm_last_kernel(void);
  *         every output is f32 (STORE / SWIGLU / ROPE write f32 [M,ldo]; act = exact erf GELU / ReLU); K % 64 == 0; PATCH and a_norm_*
  *         are rejected.  Needs split_ws (below).  Internally: split A -> bf16 [M, 3 K] (hi | hi | lo), ONE bf16 GEMM with K' = 3 K and
  *         fp32 output on the kernels above, then the activation / SwiGLU / RoPE as an fp32 row pass.
+ * Memory regions.  Never read: A columns [K, lda), A rows >= M (a tile overhanging M re-reads row M - 1) and, with a_rows_per_batch, the rows between the
+ *         row groups; W columns [K, ldw) (PATCH: up to the packer's zero-padded K); resid columns [N, ldr) and rows >= M; bias / rope tables behind N /
+ *         rope_seq rows; frames behind n_frames.  a_norm_x: columns [K, a_norm_ldx) and rows >= M.  Read, weightless: nothing.  Never written: out columns
+ *         [N', ldo) (N' = N, N / 2 for SWIGLU, 3 N' for STLLM_SPLIT_OUT), rows >= M, the rows between o_rows_per_batch groups; PATCH writes rows
+ *         n * 257 + 1 .. + 256 only (the CLS rows n * 257 are stllm_vit_cls_rows').  workspace: flags must be zero at allocation; the partial slabs and
+ *         split_ws need no initialisation.  Holds for every kernel family (64 x 64 / 128 x 128 tiles, stream-K, phased, one-wave w4, t1, W-direct, GEMV).
  */
 typedef struct {
   int dtype;          /* stllm_dtype */
@@ -202,6 +226,8 @@ int stllm_gemm(const stllm_gemm_args* args, void* stream);
  * Launches are seen by stllm_gemm_profile; stllm_last_kernel() names gemv_w8_kernel<...> / gemv_w8_mfma_kernel<...>.
  * Stands in for the nn.Linear calls of the one-token step (modeling_llama_mem.py:130-144, 163-166) when the weights are held in 8 bits —
  * the `device_8bit` / low-resource knob of demo.py:41, which the reference carries without an implementation.
+ * Memory regions: those of stllm_gemm.  Never read: A columns [K, lda) and rows >= M (the staged / fragment rows past M re-read row M - 1), Wq bytes
+ * [K, ldw) of a row, resid columns [N, ldr).  Never written: out columns [N', ldo), rows >= M, the rows between strided output rows.
  */
 typedef struct {
   int dtype;          /* STLLM_BF16 | STLLM_F16: A and the 16-bit outputs */
@@ -236,6 +262,7 @@ int stllm_gemv_w8(const stllm_gemv_w8_args* args, void* stream);
  * Constraints: 1 <= M <= 16; N % 64 == 0; K % 128 == 0; Wq 16-byte aligned, ldw % 16 == 0; A / out / resid as for stllm_gemm.
  * A shape or option combination no kernel covers returns STLLM_ERR_UNSUPPORTED (stllm_last_error() says which): nothing else runs in its place.
  * Launches are seen by stllm_gemm_profile; stllm_last_kernel() names gemv_q4_kernel<...> / gemv_q4_mfma_kernel<...>.
+ * Memory regions: those of stllm_gemv_w8; Wq bytes [K / 2, ldw) of a row and scale columns [K / 128, ld_scale) are never read.
  */
 typedef struct {
   int dtype;          /* STLLM_BF16 | STLLM_F16: A and the 16-bit outputs */
@@ -388,6 +415,10 @@ int stllm_qformer_layers(const stllm_qformer_layers_args* args, const stllm_qfor
  * several workgroups per head and the partial softmax states are merged by a second launch.  head_dim 128, bf16 / fp16.
  * q: element (b, h, d) at q[b*q_bs + h*128 + d];  k, v: (b, s, h, d) at k[b*k_bs + s*k_rs + h*128 + d];  out like q.
  * workspace: >= stllm_attention_decode_workspace_bytes(B, H, Skv) bytes, 16-byte aligned, no initialisation needed.
+ * Memory regions.  Never read: K / V rows at or behind Skv of every batch row (the cache rows the step has not reached are uninitialised), the columns
+ * of a row outside head h's 128, q / k / v behind H * 128 columns.  Read, weightless: nothing (a key that is not loaded contributes through a `live`
+ * predicate, not through a zero weight).  Never written: out behind H * 128 columns of a row, rows other than b * o_bs.  Every workspace record the merge
+ * reads was written by the partial pass of the same call.
  */
 int64_t stllm_attention_decode_workspace_bytes(int B, int H, int Skv);
 int stllm_attention_decode(int dtype, const void* q, int64_t q_bs, const void* k, int64_t k_bs, int64_t k_rs,
@@ -402,6 +433,10 @@ int stllm_attention_decode(int dtype, const void* q, int64_t q_bs, const void* k
  * Skv = kv_len[b] whenever that call takes the same schedule: same key-to-lane assignment, and in the split pair the split count and keys per split of its
  * own length, merged in the same order.  bf16 / fp16 at head_dim 128 only: anything else returns STLLM_ERR_UNSUPPORTED (fp32: stllm_attention with kv_len).
  * Addressing as for stllm_attention_decode; workspace: >= stllm_attention_decode_ragged_workspace_bytes(B, H, max_kv) bytes, 16-byte aligned.
+ * Memory regions.  Never read: K / V rows at or behind min(kv_len[b], max_kv) of batch row b; q, K and V of a row with kv_len[b] <= 0 altogether (a free
+ * slot's query is whatever the scratch held).  Read, weightless: nothing.  Written: every out row b at columns [0, H * 128), zeros for a free slot whatever
+ * the buffer held before; nothing else.  Workspace: the surplus split workgroups of a short row (split index >= that row's split count) exit without
+ * writing, and the merge reads exactly the records its row's own split count names — an unwritten record is never read.
  */
 int64_t stllm_attention_decode_ragged_workspace_bytes(int B, int H, int max_kv);
 int stllm_attention_decode_ragged(int dtype, const void* q, int64_t q_bs, const void* k, int64_t k_bs, int64_t k_rs,
@@ -421,6 +456,10 @@ int stllm_attention_decode_ragged(int dtype, const void* q, int64_t q_bs, const 
  *   fp32: one vector kernel (the verify mode), any Sq.
  * head_dim 128 only; anything unsupported returns STLLM_ERR_UNSUPPORTED (stllm_last_error() says what): nothing else runs in its place.
  * workspace: >= stllm_attention_shared_workspace_bytes(B, G, H, Sq, P, max_sfx) bytes, 16-byte aligned, no initialisation needed (unused in fp32).
+ * Memory regions.  Never read: prefix rows at or behind P, suffix rows at or behind min(sfx_len[b], max_sfx) of row b — in the Sq > 1 suffix pass the tile
+ * kernel runs with LIVE loads (rows behind the length are replaced by zeros in the LDS instead of being loaded).  Read, weightless: nothing.  Pad query rows
+ * (Sq > 1, i >= the row's own new tokens) are read and their output rows are written with don't-care (finite-or-not) values: the caller ignores them.
+ * Never written: kp / vp / ks / vs; out behind H * 128 columns.  Workspace records: written by the partial pass before the merge reads them.
  */
 int64_t stllm_attention_shared_workspace_bytes(int B, int G, int H, int Sq, int P, int max_sfx);
 int stllm_attention_shared(int dtype, const void* q, int64_t q_bs, int64_t q_rs, const void* kp, int64_t kp_bs, int64_t kp_rs,
@@ -435,6 +474,8 @@ int stllm_attention_shared(int dtype, const void* q, int64_t q_bs, int64_t q_rs,
  * outside [0, max_len) marks a free slot: nothing is written for that row.  All strides in elements of `dtype` (bf16 / fp16 / fp32).  16-byte vector
  * copies: pointers, hidden * esize and every stride * esize must be multiples of 16 bytes.  The QKV GEMV writes rows at ONE stride only, so a ragged
  * decode step lets it write a dense [B, 3*hidden] scratch and scatters from there.
+ * Memory regions.  Never read: src row b of a free slot; the q columns of src unless with_q.  Never written: any cache row other than (b, pos[b]), the q
+ * columns of that row unless with_q, anything at all for a free slot (the one place where a logical output row is deliberately left as it was).
  */
 int stllm_kv_append_rows(int dtype, const void* src, int64_t ld_src, void* cache, int64_t batch_stride, int64_t row_stride,
                          const int32_t* pos, int B, int hidden, int max_len, int with_q, void* stream);
@@ -461,6 +502,8 @@ int stllm_preprocess_frames(const uint8_t* frames, int64_t frame_stride_bytes, i
  * Replaces nn.LayerNorm at eva_vit.py:157,163 (eps 1e-6), blip2.py:103-109 (ln_vision, eps 1e-5),
  * Qformer.py:65,106,282,288,368,374 (eps 1e-12), st_llm.py:39 (mvm_decoder.norm).
  * D % 4 == 0, D <= 8192.
+ * Memory regions (stllm_layernorm and stllm_rmsnorm).  Never read: x columns [D, ldx), rows >= M.  Never written: out_t columns [D, ldo_t) ([3 D, ldo_t)
+ * for STLLM_BF16X3), out_f32 columns [D, ldo_f), rows >= M of either.
  */
 int stllm_layernorm(int dtype, const float* x, int64_t ldx, const float* gamma, const float* beta,
                     float eps, void* out_t, int64_t ldo_t, float* out_f32, int64_t ldo_f,
@@ -480,6 +523,13 @@ int stllm_rmsnorm(int dtype, const float* x, int64_t ldx, const float* gamma, fl
  *         Qformer.py:785-801 with -10000 == exact 0 after fp32 softmax).
  * causal: key j visible to query i iff j <= i (Sq == Skv).
  * D in {64, 88, 128}; all strides multiples of 8 elements; pointers 16-byte aligned.
+ * Memory regions.  Never read: q rows >= Sq and K / V rows >= Skv of a batch entry (a key tile overhanging Skv is filled with zeros in the LDS, not
+ * loaded), columns behind H * D.  READ, WEIGHTLESS, MUST BE FINITE: the K / V rows in [kv_len[b], Skv).  The tile kernels load whole key tiles up to Skv
+ * and mask the SCORES; a masked probability is an exact 0, and 0 x NaN in V would reach the output — so the caller must have written finite values there
+ * (the prefill does: they are the projections of the pad positions).  Memory that may be uninitialised behind a length belongs behind Skv, or to
+ * stllm_attention_decode_ragged / stllm_attention_shared, which bound their loads by the length.  (The fp32 one-wave-per-row vector kernel bounds its key loop by
+ * kv_len; the fp32 matrix-core kernel loads up to Skv like the 16-bit ones: callers must not rely on which kernel runs.)  Query rows at or behind kv_len[b] of a causal call are ordinary rows: read, and their
+ * outputs written (they attend the valid keys).  Never written: out behind H * D columns of a row, rows >= Sq of a batch entry.
  */
 int stllm_attention(int dtype, const void* q, int64_t q_bs, int64_t q_rs,
                     const void* k, int64_t k_bs, int64_t k_rs,
@@ -496,6 +546,9 @@ int stllm_attention(int dtype, const void* q, int64_t q_bs, int64_t q_rs,
  * partial softmax states in `workspace`, a second launch merges them in a fixed order (deterministic) —, everything else the register-staged tile kernels.
  * workspace: NULL (tile kernels only) or >= stllm_attention_offset_workspace_bytes(B, H, Sq, Skv) bytes, 16-byte aligned, no initialisation needed.
  * stllm_set_option("attn_ksplit", 0 / 1 / -1): never / wherever eligible / by the measured rule (default).  stllm_last_kernel() names the kernel that ran.
+ * Memory regions: those of stllm_attention — K / V rows >= Skv = q_off + Sq never read (the cache rows behind the new suffix are uninitialised), rows in
+ * [kv_len[b], Skv) read, weightless, must be finite (extend(lengths=) writes the pad rows of a short suffix before the attention runs).  The key-split
+ * workspace needs no initialisation: every partial state the merge reads was written by the first launch of the same call.
  */
 int64_t stllm_attention_offset_workspace_bytes(int B, int H, int Sq, int Skv);
 int stllm_attention_offset(int dtype, const void* q, int64_t q_bs, int64_t q_rs,

@@ -600,20 +600,26 @@ def test_scale_rows(dtype):
 def test_emulated_split_kv_decode_attention(dtype, single):
     """the one-token decode step's attention (single-pass kernel: one workgroup per head; split-KV partial + merge kernels) on a
     strided KV cache layout == contract"""
+    import _poison
     B, H, D, Skv, ML = 2, 2, 128, 100, 128                       # cache rows [B, ML, 3*H*D]; 100 keys in use
     HD = H * D
     cache = rnd(B * ML, 3 * HD, seed=120, dtype=dtype, scale=0.6)
+    cache.view(B, ML, 3 * HD)[:, Skv:] = float("nan")            # the rows at or behind Skv are never read (include/stllm_hip.h: memory regions)
     row = cache.view(B, ML, 3 * HD)[:, Skv - 1]                  # the new token's fused row (q | k | v)
     kw = dict(B=B, H=H, Sq=1, Skv=Skv, D=D, scale=D ** -0.5, causal=False, q_strides=(ML * 3 * HD, 3 * HD), k_strides=(ML * 3 * HD, 3 * HD),
               v_strides=(ML * 3 * HD, 3 * HD))
     want = C.attention(row[:, :HD], cache[:, HD:2 * HD], cache[:, 2 * HD:], **kw)
+    g = _poison.Guarded(B, HD, dtype)                            # the output inside a 0xFF-filled buffer: rows around it, columns [HD, ldo)
     with _hipemu.emulated() as hip:
         hip.set_option("attn_decode_single", single)
         try:
-            got = hip.attention(row[:, :HD], cache[:, HD:2 * HD], cache[:, 2 * HD:], **kw)
+            with _poison.poisoned_allocations() as counts:       # the partial-state workspace "needs no initialisation": 0xFF in every byte of it
+                got = hip.attention(row[:, :HD], cache[:, HD:2 * HD], cache[:, 2 * HD:], out=g.out, **kw)
         finally:
             hip.set_option("attn_decode_single", 1)
         assert hip._decode_attn
+    assert counts.allocations > 0 and g.intact(), "no byte around the output rows was written"
+    assert bool(torch.isfinite(got.float()).all())
     close(got, want, 2 * TOL[dtype], "decode attention")
 
 

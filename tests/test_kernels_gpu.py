@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 import stllm_oracle as O
+import _poison
 from _util import T
 
 pytestmark = pytest.mark.gpu
@@ -182,13 +183,74 @@ def test_gemm_two_level_rows(hip, dtype):
     w, w64 = rnd("w", (Nout, C), dtype, 0.05)
     ref_q = buf64.view(N_, S, C)[:, :Q].reshape(-1, C) @ w64.t()
     ref_t = buf64.view(N_, S, C)[:, Q:].reshape(-1, C) @ w64.t()
-    out = torch.zeros((N_ * S, Nout), device="cuda", dtype=torch.float32)
-    hip.gemm(buf, w, dtype=dtype, out=out, out_f32=True, M=N_ * Q, a_rows=(Q, S * C), o_rows=(Q, S * Nout))
-    hip.gemm(buf[Q:], w, dtype=dtype, out=out[Q:], out_f32=True, M=N_ * (S - Q), a_rows=(S - Q, S * C),
-             o_rows=(S - Q, S * Nout))
-    o = out.view(N_, S, Nout)
+    # the rows BETWEEN the row groups of a 2-level view and the columns [C, lda) are never read: NaN in the text rows for the query call, in the query
+    # rows for the text call, and behind every row; the output sits inside a 0xFF-filled buffer (rows around it, columns [Nout, ldo))
+    ld = C + 8
+    bq, bt = _poison.nan_padded(buf), _poison.nan_padded(buf)
+    bq.view(N_, S, C)[:, Q:] = float("nan")
+    bt.view(N_, S, C)[:, :Q] = float("nan")
+    g = _poison.Guarded(N_ * S, Nout, torch.float32, device="cuda")
+    out, ldo = g.out, g.out.stride(0)
+    hip.gemm(bq, w, dtype=dtype, out=out, out_f32=True, M=N_ * Q, a_rows=(Q, S * ld), o_rows=(Q, S * ldo))
+    inner = g.buf[g.before: g.before + N_ * S, :Nout].view(N_, S, Nout)
+    assert bool(torch.isnan(inner[:, Q:]).all()) and g.intact(), "the query call wrote outside its row groups"
+    hip.gemm(bt[Q:], w, dtype=dtype, out=out[Q:], out_f32=True, M=N_ * (S - Q), a_rows=(S - Q, S * ld),
+             o_rows=(S - Q, S * ldo))
+    assert g.intact(), "a byte outside the N_ * S x Nout output was written"
+    o = out.reshape(N_, S, Nout)
     check(o[:, :Q].reshape(-1, Nout), ref_q, ACC_TOL[dtype], "query rows")
     check(o[:, Q:].reshape(-1, Nout), ref_t, ACC_TOL[dtype], "text rows")
+
+
+# one ragged-M case per GEMM family the tests can force: a row count ONE above a tile multiple (where a tail store goes wrong), A with a leading dimension
+# larger than K and NaN in the columns [K, lda), the residual likewise in [N, ldr), every output inside a 0xFF-filled buffer (rows in front of and behind
+# it, columns [N, ldo)) whose guard bytes must be unchanged after the call.  (option, value, tile rows, N, K, kernel-name prefix | None)
+GUARD_FAMILIES = [("base 64 x 64", None, 0, 64, 128, 128, None)] + \
+    [(f"phased miw {m}", "gemm_p8", m, 64 * m, 256, 1408, "gemm_p8_kernel<") for m in (3, 4)] + \
+    [(f"w4 {c}", "gemm_w4", c, 64 * (c // 10), 384, 1408, "gemm_w4_kernel<") for c in (32, 34, 42, 24, 22)] + \
+    [(f"w4 {c}", "gemm_w4", c, 64 * (c // 10), 384, 256, "gemm_w4_kernel<") for c in (43, 33)] + \
+    [("t1", "gemm_t1", 2, 144, 128, 1408, "gemm_t1_kernel<")] + \
+    [(f"wd wm {m}", "gemm_wd", m, 32 * m, 256, 512, "gemm_wd_kernel<") for m in (4, 6)] + \
+    [(f"stream-K bm {m}", "gemm_sk", m, 256, 256, 1408, "gemm_sk_kernel<") for m in (1, 2, 3)]
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("name,opt,val,rows,N,K,prefix", GUARD_FAMILIES, ids=[f[0] for f in GUARD_FAMILIES])
+def test_gemm_write_guards_at_ragged_m(hip, dtype, name, opt, val, rows, N, K, prefix):
+    from stllm_amd import pack
+    M = rows + 1
+    td = hip.torch_dtype(dtype)
+    if opt is None:
+        hip.set_option("gemm_w4", 0); hip.set_option("gemm_p8", 0)      # the automatic families off: the base tile kernels
+    else:
+        hip.set_option(opt, val)
+    try:
+        a, a64 = rnd("a", (M, K), dtype, 0.5)
+        w, w64 = rnd("w", (N, K), dtype, 0.05)
+        kw = dict(w_frag=pack.frag32(w)) if opt == "gemm_wd" else {}
+        b = T("b", (N,), 0.5)
+        ref = a64 @ w64.t() + b.double()
+        a = _poison.nan_padded(a)
+        g32, g16, gr = (_poison.Guarded(M, N, t, device="cuda") for t in (torch.float32, td, torch.float32))
+        odd = opt == "gemm_w4" and val in (43, 33)   # the 192-column tiles serve 16-bit STORE outputs without a K-split only: the other two calls fall back
+        out = hip.gemm(a, w, dtype=dtype, bias=b.cuda(), out_f32=True, out=g32.out, **kw)
+        ran = hip.lib().stllm_last_kernel().decode()
+        assert prefix is None or odd or ran.startswith(prefix), (name, ran)
+        check(out, ref, ACC_TOL[dtype], f"{name}: store f32 ({ran})")
+        check(hip.gemm(a, w, dtype=dtype, bias=b.cuda(), out=g16.out, **kw), ref, OUT_TOL[dtype], f"{name}: store T")
+        ran16 = hip.lib().stllm_last_kernel().decode()
+        assert prefix is None or ran16.startswith(prefix), (name, ran16)
+        x = T("x", (M, N), 2.0)
+        xd = _poison.nan_padded(x.cuda())
+        hip.gemm(a, w, dtype=dtype, epilogue=hip.EPI_RESID, bias=b.cuda(), resid=xd, out=gr.out, **kw)
+        check(gr.out, x.double() + ref, ACC_TOL[dtype], f"{name}: resid out of place ({hip.lib().stllm_last_kernel().decode()})")
+        assert g32.intact() and g16.intact() and gr.intact(), f"{name}: a byte outside the M x N output was written"
+        assert hip.gemm_workspace_ok(), hip.lib().stllm_last_error().decode()
+    finally:
+        if opt is None:
+            hip.set_option("gemm_w4", -1); hip.set_option("gemm_p8", -1)
+        else:
+            hip.set_option(opt, -1)
 
 
 SK_SHAPES = [(4112 // 2, 4224, 1408), (576, 4096, 4096), (576, 1536, 11008 // 2), (300, 768, 3072), (97, 256, 6144), (1, 128, 128 * 7)]
@@ -982,14 +1044,19 @@ def _gemv_decode_regime(hip, dtype, M, N, K, want):
     w, w64 = rnd("w", (N, K), dtype, 0.05)
     b = T("b", (N,), 0.5)
     ref = a64 @ w64.t() + b.double()
-    out = hip.gemm(a, w, dtype=dtype, bias=b.cuda(), out_f32=True)
+    a = _poison.nan_padded(a)                                                   # A columns [K, lda): NaN, never read
+    g32 = _poison.Guarded(M, N, torch.float32, device="cuda")                   # outputs inside 0xFF-filled buffers: rows around them, columns [N, ldo)
+    out = hip.gemm(a, w, dtype=dtype, bias=b.cuda(), out_f32=True, out=g32.out)
     assert hip.lib().stllm_last_kernel().decode().startswith(want), (hip.lib().stllm_last_kernel().decode(), want)
     check(out, ref, ACC_TOL[dtype], "gemv store f32")
-    check(hip.gemm(a, w, dtype=dtype, bias=b.cuda(), act=hip.ACT_GELU), O.gelu(ref), OUT_TOL[dtype], "gemv gelu T")
+    g16 = _poison.Guarded(M, N, hip.torch_dtype(dtype), device="cuda")
+    check(hip.gemm(a, w, dtype=dtype, bias=b.cuda(), act=hip.ACT_GELU, out=g16.out), O.gelu(ref), OUT_TOL[dtype], "gemv gelu T")
+    assert g32.intact() and g16.intact(), "gemv: a byte outside the M x N output was written"
     x = T("x", (M, N), 2.0)
-    xd = x.cuda()
+    xd = _poison.nan_padded(x.cuda())                                           # resid columns [N, ldr): NaN, never read, never written
     hip.gemm(a, w, dtype=dtype, epilogue=hip.EPI_RESID, bias=b.cuda(), resid=xd)
     check(xd, x.double() + ref, ACC_TOL[dtype], "gemv resid")
+    assert bool(torch.isnan(torch.as_strided(xd, (M, 8), (xd.stride(0), 1), xd.storage_offset() + N)).all()), "gemv resid: the columns [N, ldr) were written"
     # output rows with a stride (the decode step writes one row per sequence into the KV cache buffer)
     buf = torch.zeros((M, 3, N), device="cuda", dtype=hip.torch_dtype(dtype))
     hip.gemm(a, w, dtype=dtype, out=buf[:, 1])
@@ -1033,12 +1100,16 @@ def test_attention_decode_split_kv(hip, dtype, B, H, Skv, single):
     D, max_len = 128, Skv + 5
     td = hip.torch_dtype(dtype)
     cache, c64 = rnd("kvcache", (B * max_len, 3 * H * D), dtype)
+    cache.view(B, max_len, 3 * H * D)[:, Skv:] = float("nan")                  # the cache rows at or behind Skv are never read (stllm_hip.h: memory regions)
     full = cache.view(B * max_len, 3 * H * D)
     row = cache.view(B, max_len, 3 * H * D)[:, Skv - 1]                       # the newest token's fused QKV row: [B, 3HD] strided view
     ML3 = max_len * 3 * H * D
     kw = dict(B=B, H=H, Sq=1, Skv=Skv, D=D, scale=D ** -0.5, causal=False, q_strides=(ML3, 3 * H * D), k_strides=(ML3, 3 * H * D),
               v_strides=(ML3, 3 * H * D))
-    got = hip.attention(row[:, :H * D], full[:, H * D:2 * H * D], full[:, 2 * H * D:], **kw)
+    g = _poison.Guarded(B, H * D, td, device="cuda")                           # the output inside a 0xFF-filled buffer: rows around it, columns [HD, ldo)
+    with _poison.poisoned_allocations() as counts:                              # the partial-state workspace "needs no initialisation": 0xFF in every byte
+        got = hip.attention(row[:, :H * D], full[:, H * D:2 * H * D], full[:, 2 * H * D:], out=g.out, **kw)
+    assert counts.allocations > 0 and g.intact(), "a byte outside the output rows was written"
     c = c64.view(B, max_len, 3, H, D)
     q = c[:, Skv - 1, 0]                                                        # [B, H, D]
     k, v = c[:, :Skv, 1].transpose(1, 2), c[:, :Skv, 2].transpose(1, 2)        # [B, H, Skv, D]
@@ -1096,13 +1167,18 @@ def test_layernorm_rmsnorm(hip, dtype, D):
     g = T("g", (D,), 0.2) + 1.0
     b = T("b", (D,), 0.1)
     ref = F.layer_norm(x.double(), (D,), g.double(), b.double(), 1e-6)
-    ot, of = hip.layernorm(x.cuda(), g.cuda(), b.cuda(), 1e-6, dtype=dtype, want_f32=True)
+    xd = _poison.nan_padded(x.cuda())                                           # x columns [D, ldx): NaN, never read
+    gt, gf = _poison.Guarded(M, D, hip.torch_dtype(dtype), device="cuda"), _poison.Guarded(M, D, torch.float32, device="cuda")
+    ot, of = hip.layernorm(xd, g.cuda(), b.cuda(), 1e-6, dtype=dtype, out_t=gt.out, out_f32=gf.out)
     check(of, ref, 2e-6, "layernorm f32")
     check(ot, ref, OUT_TOL[dtype], "layernorm T")
+    assert gt.intact() and gf.intact(), "layernorm: a byte outside the M x D outputs was written"
     ref = O.rms_norm(x.double(), g.double(), 1e-6)
-    ot, of = hip.rmsnorm(x.cuda(), g.cuda(), 1e-6, dtype=dtype, want_f32=True)
+    gt, gf = _poison.Guarded(M, D, hip.torch_dtype(dtype), device="cuda"), _poison.Guarded(M, D, torch.float32, device="cuda")
+    ot, of = hip.rmsnorm(xd, g.cuda(), 1e-6, dtype=dtype, out_t=gt.out, out_f32=gf.out)
     check(of, ref, 2e-6, "rmsnorm f32")
     check(ot, ref, OUT_TOL[dtype], "rmsnorm T")
+    assert gt.intact() and gf.intact(), "rmsnorm: a byte outside the M x D outputs was written"
 
 
 def _attn_ref(q, k, v, scale, causal, kv_len):
@@ -1152,7 +1228,18 @@ def _attention_case(hip, dtype, case):
     _, B, H, Sq, Skv, D, causal, kv_len = case
     # q/k/v as column slices of one fused buffer, exactly how the model calls it
     C = 3 * H * D
-    if Sq == Skv:
+    strides = {}
+    if Sq == Skv and kv_len is not None:
+        # K and V inside buffers LONGER than Skv whose rows at or behind Skv are NaN: never read.  The rows in [kv_len, Skv) stay finite random: the tile
+        # kernels load them by design — read, weightless, must be finite (include/stllm_hip.h: memory regions)
+        ML = Skv + 3
+        big, big64 = rnd("qkv", (B, ML, C), dtype)
+        big[:, Skv:] = float("nan")
+        buf, buf64 = big.view(B * ML, C), big64[:, :Skv].reshape(B * Skv, C)
+        q, k, v = buf[:, :H * D], buf[:, H * D:2 * H * D], buf[:, 2 * H * D:]
+        q64, k64, v64 = [buf64[:, i * H * D:(i + 1) * H * D].reshape(B, Sq, H, D).transpose(1, 2) for i in range(3)]
+        strides = dict(q_strides=(ML * C, C), k_strides=(ML * C, C), v_strides=(ML * C, C))
+    elif Sq == Skv:
         buf, buf64 = rnd("qkv", (B * Sq, C), dtype)
         q, k, v = buf[:, :H * D], buf[:, H * D:2 * H * D], buf[:, 2 * H * D:]
         q64, k64, v64 = [buf64[:, i * H * D:(i + 1) * H * D].reshape(B, Sq, H, D).transpose(1, 2) for i in range(3)]
@@ -1166,7 +1253,9 @@ def _attention_case(hip, dtype, case):
     scale = D ** -0.5
     ref = _attn_ref(q64, k64, v64, scale, causal, kv_len).transpose(1, 2).reshape(B * Sq, H * D)
     kl = None if kv_len is None else torch.tensor(kv_len, dtype=torch.int32).cuda()
-    out = hip.attention(q, k, v, B=B, H=H, Sq=Sq, Skv=Skv, D=D, scale=scale, causal=causal, kv_len=kl)
+    g = _poison.Guarded(B * Sq, H * D, hip.torch_dtype(dtype), device="cuda")   # the output inside a 0xFF-filled buffer: rows around it, columns [HD, ldo)
+    out = hip.attention(q, k, v, B=B, H=H, Sq=Sq, Skv=Skv, D=D, scale=scale, causal=causal, kv_len=kl, out=g.out, **strides)
+    assert g.intact(), "attention: a byte outside the B * Sq x HD output was written"
     if kv_len is not None and causal:
         # padded query rows are defined (attend to the valid keys) — compared as well
         pass

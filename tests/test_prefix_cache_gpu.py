@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+import _poison
+
 from _util import T, golden
 
 pytestmark = pytest.mark.gpu
@@ -56,6 +58,7 @@ def test_offset_attention_matches_fp64(hip, dtype, Sq, q_off):
     k64 = buf[:, :Skv, HD:2 * HD].double().view(B, Skv, H, D)
     v64 = buf[:, :Skv, 2 * HD:].double().view(B, Skv, H, D)
     ref = dense_ref(q64, k64, v64, q_off)
+    buf[:, Skv:] = float("nan")                  # the cache rows at or behind Skv are never read (include/stllm_hip.h: memory regions)
     dbuf = buf.cuda()
     full = dbuf.view(B * ML, 3 * HD)
     st = (ML * 3 * HD, 3 * HD)
@@ -63,8 +66,12 @@ def test_offset_attention_matches_fp64(hip, dtype, Sq, q_off):
     try:
         for opt in (0, 1, -1):
             hip.set_option("attn_ksplit", opt)
-            out = hip.attention(full[q_off:, :HD], full[:, HD:2 * HD], full[:, 2 * HD:], B=B, H=H, Sq=Sq, Skv=Skv, D=D, scale=D ** -0.5, causal=True,
-                                q_strides=st, k_strides=st, v_strides=st, q_off=q_off)
+            g = _poison.Guarded(B * Sq, HD, td, device="cuda")            # the output inside a 0xFF-filled buffer: rows around it, columns [HD, ldo)
+            with _poison.poisoned_allocations() as counts:                 # the key-split workspace "needs no initialisation": 0xFF in every byte
+                out = hip.attention(full[q_off:, :HD], full[:, HD:2 * HD], full[:, 2 * HD:], B=B, H=H, Sq=Sq, Skv=Skv, D=D, scale=D ** -0.5, causal=True,
+                                    q_strides=st, k_strides=st, v_strides=st, q_off=q_off, out=g.out)
+            assert g.intact(), "a byte outside the output rows was written"
+            assert counts.allocations > 0 or dtype == "fp32"
             ran = hip.lib().stllm_last_kernel().decode()
             if dtype == "fp32":
                 assert ran in ("attn_mfma_f32_kernel", "attn_f32_kernel"), ran
@@ -73,7 +80,7 @@ def test_offset_attention_matches_fp64(hip, dtype, Sq, q_off):
             check(out, ref, tol, f"offset attention {dtype} Sq={Sq} q_off={q_off} attn_ksplit={opt} -> {ran}")
     finally:
         hip.set_option("attn_ksplit", -1)
-    assert torch.equal(dbuf.cpu(), buf), "the cache buffer is read-only for the attention"
+    assert _poison.bits_equal(dbuf.cpu(), buf), "the cache buffer is read-only for the attention"
 
 
 def _last_logits(model, h16, B, S):

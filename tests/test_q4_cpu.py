@@ -130,19 +130,28 @@ def q4_case(hip, dtype, M, N, K, want, dev=lambda t: t, full=True):
     qp, scale = pack.quant4_groups(T("q4.w", (N, K), 0.05).to(td))
     b = T("q4.b", (N,), 0.5)
     ref = a.double() @ deq(qp, scale).t() + b.double()
-    ad, qd, sd, bd = dev(a), dev(qp), dev(scale), dev(b)
+    import _poison
+    # a leading dimension larger than K with NaN in the columns [K, lda): never read (include/stllm_hip.h: memory regions)
+    ad, qd, sd, bd = _poison.nan_padded(dev(a)), dev(qp), dev(scale), dev(b)
     q0, s0 = qd.clone(), sd.clone()
     if want is None:
         with pytest.raises(RuntimeError, match="no kernel for M="):
             hip.gemv_q4(ad, qd, sd, dtype=dtype, out_f32=True)
         return
-    out = hip.gemv_q4(ad, qd, sd, dtype=dtype, bias=bd, out_f32=True)
+    g32 = _poison.Guarded(M, N, torch.float32, device=ad.device)     # the output inside a 0xFF-filled buffer: rows around it, columns [N, ldo)
+    out = hip.gemv_q4(ad, qd, sd, dtype=dtype, bias=bd, out_f32=True, out=g32.out)
     _ran(hip, want, "store f32")
     _check(out, ref, ACC_TOL[dtype], "q4 store f32")
+    assert g32.intact(), "q4 store f32: a byte outside the M x N output was written"
     x = T("q4.x", (M, N), 2.0)
-    xd = dev(x.clone())
+    xd = _poison.nan_padded(dev(x.clone()))                          # resid columns [N, ldr): NaN, never read, never written
     hip.gemv_q4(ad, qd, sd, dtype=dtype, epilogue=hip.EPI_RESID, bias=bd, resid=xd)
     _check(xd, x.double() + ref, ACC_TOL[dtype], "q4 resid")
+    assert bool(torch.isnan(torch.as_strided(xd, (M, 8), (xd.stride(0), 1), xd.storage_offset() + N)).all()), "q4 resid: the columns [N, ldr) were written"
+    g16 = _poison.Guarded(M, N, td, device=ad.device)
+    o16 = hip.gemv_q4(ad, qd, sd, dtype=dtype, bias=bd, out=g16.out)
+    _check(o16, ref, OUT_TOL[dtype], "q4 store T")
+    assert g16.intact(), "q4 store T: a byte outside the M x N output was written"
     buf = dev(torch.zeros((M, 3, N), dtype=td))       # output rows with a stride, untouched neighbours
     hip.gemv_q4(ad, qd, sd, dtype=dtype, out=buf[:, 1])
     _check(buf[:, 1], ref - b.double(), OUT_TOL[dtype], "q4 strided rows")

@@ -55,22 +55,30 @@ def test_emulated_ragged_decode_attention(dtype, lens, single, what):
     """stllm_attention_decode_ragged (attn_decode_single_ragged / attn_decode_partial_ragged + attn_decode_merge_ragged) on a strided cache with q in a dense
     scratch row: every row against fp64 of the same 16-bit inputs (the bound of test_emulated_split_kv_decode_attention: 2 x one output rounding step), a
     zero-length row gives zeros, and every row is bit-identical to stllm_attention_decode on that row alone with Skv = lens[b] when both take one schedule"""
+    import _poison
     B, H, D = len(lens), 1, 128
     HD = H * D
     ML = max(lens) + 3
     cache = rnd(B, ML, 3 * HD, seed=300 + len(lens), dtype=dtype, scale=0.6)
     q = rnd(B, 3 * HD, seed=301, dtype=dtype, scale=0.6)
+    for b, n in enumerate(lens):
+        cache[b, n:] = float("nan")                             # the rows at or behind a row's length are uninitialised memory: never read
+        if n == 0:
+            q[b] = float("nan")                                 # ... and so is the query of a free slot
     kv_len = torch.tensor(lens, dtype=torch.int32)
     flat = cache.view(B * ML, 3 * HD)
     strides = (ML * 3 * HD, 3 * HD)
     want = fp64_rows(q, cache, lens, H, D)
+    g = _poison.Guarded(B, HD, dtype)                           # the output starts as 0xFF (NaN) inside a 0xFF-filled buffer: a free slot must still read zeros
     with _hipemu.emulated() as hip:
         hip.set_option("attn_decode_single", single)
         try:
-            got = hip.attention_decode_ragged(q[:, :HD], flat[:, HD:2 * HD], flat[:, 2 * HD:], kv_len, B=B, H=H, max_kv=max(lens), D=D, scale=D ** -0.5,
-                                              q_stride=3 * HD, k_strides=strides, v_strides=strides)
-            routed = hip.attention(q[:, :HD], flat[:, HD:2 * HD], flat[:, 2 * HD:], B=B, H=H, Sq=1, Skv=max(lens), D=D, scale=D ** -0.5, kv_len=kv_len,
-                                   q_strides=(3 * HD, 3 * HD), k_strides=strides, v_strides=strides)
+            with _poison.poisoned_allocations() as counts:      # the partial-state workspace: 0xFF in every byte (a merge that read an unwritten record would see it)
+                got = hip.attention_decode_ragged(q[:, :HD], flat[:, HD:2 * HD], flat[:, 2 * HD:], kv_len, B=B, H=H, max_kv=max(lens), D=D, scale=D ** -0.5,
+                                                  q_stride=3 * HD, k_strides=strides, v_strides=strides, out=g.out)
+                routed = hip.attention(q[:, :HD], flat[:, HD:2 * HD], flat[:, 2 * HD:], B=B, H=H, Sq=1, Skv=max(lens), D=D, scale=D ** -0.5, kv_len=kv_len,
+                                       q_strides=(3 * HD, 3 * HD), k_strides=strides, v_strides=strides)
+            assert counts.allocations >= 2 and g.intact(), "no byte around the output rows was written"
             assert torch.equal(got, routed), "hip.attention(Sq=1, kv_len=...) routes to the ragged decode kernels"
             split_all = single == 0 or max(lens) > 1536
             for b, n in enumerate(lens):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import _poison
 from _util import T
 from test_kernels_gpu import OUT_TOL, check
 
@@ -56,15 +57,22 @@ def test_attention_decode_ragged(hip, dtype, B, single):
     td = hip.torch_dtype(dtype)
     cache = T("ragged.kvcache", (B, ML, 3 * H * D), 1.0).to(td).cuda()
     q = T("ragged.q", (B, 3 * H * D), 1.0).to(td).cuda()
+    for b, n in enumerate(lens):
+        cache[b, n:] = float("nan")                          # the rows at or behind a row's length are uninitialised memory: never read
+        if n == 0:
+            q[b] = float("nan")                              # ... and so is the query of a free slot
     kv_len = torch.tensor(lens, dtype=torch.int32).cuda()
     full = cache.view(B * ML, 3 * H * D)
     ks = (ML * 3 * H * D, 3 * H * D)
     ragged_single = single == 1 and (max_kv <= 1536 or B * H >= 256)
     hip.set_option("attn_decode_single", single)
     try:
-        got = hip.attention(q[:, :H * D], full[:, H * D:2 * H * D], full[:, 2 * H * D:], B=B, H=H, Sq=1, Skv=max_kv, D=D, scale=D ** -0.5, kv_len=kv_len,
-                            q_strides=(3 * H * D, 3 * H * D), k_strides=ks, v_strides=ks)
+        g = _poison.Guarded(B, H * D, td, device="cuda")     # the output starts as 0xFF (NaN) inside a 0xFF-filled buffer: a free slot must still read zeros
+        with _poison.poisoned_allocations() as counts:       # the partial-state workspace: 0xFF in every byte (a merge that read an unwritten record would see it)
+            got = hip.attention(q[:, :H * D], full[:, H * D:2 * H * D], full[:, 2 * H * D:], B=B, H=H, Sq=1, Skv=max_kv, D=D, scale=D ** -0.5, kv_len=kv_len,
+                                q_strides=(3 * H * D, 3 * H * D), k_strides=ks, v_strides=ks, out=g.out)
         torch.cuda.synchronize()
+        assert counts.allocations > 0 and g.intact(), "a byte outside the output rows was written"
         n_same = 0
         for b, n in enumerate(lens):
             if n == 0:

@@ -284,3 +284,27 @@ def test_emulated_shared_decode_attention(dtype):
         err = float((got[b].double() - want[b]).abs().max())
         print(f"shared decode attention {dtype} row {b} (suffix {sfx[b]}): err {err:.3e} / abs-max {scale:.3e}")
         assert err <= 2 * OUT_TOL[dtype] * scale, (b, err, scale)
+
+
+@needs_emu
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_emulated_shared_extend_attention(dtype):
+    """stllm_attention_shared, Sq > 1 (extend(lengths=) behind a shared base): H = 1, G = 1, R = 3, P = 33, Sq = 8 causal query rows per batch row, ragged
+    suffix lengths [8, 5, 1] — the suffix pass is attn_mfma_kernel with LIVE loads, the only tile-kernel instantiation that does not load the key rows
+    behind a row's length.  Everything behind P and behind every suffix length is NaN, and the partial-state workspace is poisoned: the live query rows
+    against fp64 within 2 x OUT_TOL (the bound of tests/test_shared_prefix_gpu.py::test_attention_shared_extend), finite."""
+    import _poison
+    td = {"bf16": torch.bfloat16, "fp16": torch.float16}[dtype]
+    G, R, H, P, Sq, sfx = 1, 3, 1, 33, 8, [8, 5, 1]
+    pre, suf, q = SC.make(td, G, R, H, P, sfx, Sq=Sq)
+    want, live = SC.reference(pre, suf, q, G, R, H, P, sfx, Sq=Sq, causal=True, q_off=0)
+    with _hipemu.emulated() as hip:
+        with _poison.poisoned_allocations() as counts:
+            got = SC.call(hip, pre, suf, q, G, R, H, P, sfx, Sq=Sq, causal=True, q_off=0)
+    live = live.reshape(-1)
+    assert counts.count > 0
+    assert torch.isfinite(got[live].float()).all(), "something behind P or behind a suffix length was read"
+    scale = float(want.abs().max())
+    err = float((got[live].double() - want[live]).abs().max())
+    print(f"shared extend attention {dtype}: err {err:.3e} / abs-max {scale:.3e}")
+    assert err <= 2 * OUT_TOL[dtype] * scale, (err, scale)

@@ -117,19 +117,28 @@ def w8_case(hip, dtype, M, N, K, want, dev=lambda t: t, full=True):
     b = T("w8.b", (N,), 0.5)
     a64, q64, s64 = a.double(), q.double(), scale.double()
     ref = (a64 @ q64.t()) * s64 + b.double()
-    ad, qd, sd, bd = dev(a), dev(q), dev(scale), dev(b)
+    import _poison
+    # a leading dimension larger than K with NaN in the columns [K, lda): never read (include/stllm_hip.h: memory regions)
+    ad, qd, sd, bd = _poison.nan_padded(dev(a)), dev(q), dev(scale), dev(b)
     q0, s0 = qd.clone(), sd.clone()
     if want is None:
         with pytest.raises(RuntimeError, match="no kernel for M="):
             hip.gemv_w8(ad, qd, sd, dtype=dtype, out_f32=True)
         return
-    out = hip.gemv_w8(ad, qd, sd, dtype=dtype, bias=bd, out_f32=True)
+    g32 = _poison.Guarded(M, N, torch.float32, device=ad.device)     # the output inside a 0xFF-filled buffer: rows around it, columns [N, ldo)
+    out = hip.gemv_w8(ad, qd, sd, dtype=dtype, bias=bd, out_f32=True, out=g32.out)
     _ran(hip, want, "store f32")
     _check(out, ref, ACC_TOL[dtype], "w8 store f32")
+    assert g32.intact(), "w8 store f32: a byte outside the M x N output was written"
     x = T("w8.x", (M, N), 2.0)
-    xd = dev(x.clone())
+    xd = _poison.nan_padded(dev(x.clone()))                          # resid columns [N, ldr): NaN, never read, never written
     hip.gemv_w8(ad, qd, sd, dtype=dtype, epilogue=hip.EPI_RESID, bias=bd, resid=xd)
     _check(xd, x.double() + ref, ACC_TOL[dtype], "w8 resid")
+    assert bool(torch.isnan(torch.as_strided(xd, (M, 8), (xd.stride(0), 1), xd.storage_offset() + N)).all()), "w8 resid: the columns [N, ldr) were written"
+    g16 = _poison.Guarded(M, N, td, device=ad.device)
+    o16 = hip.gemv_w8(ad, qd, sd, dtype=dtype, bias=bd, out=g16.out)
+    _check(o16, ref, OUT_TOL[dtype], "w8 store T")
+    assert g16.intact(), "w8 store T: a byte outside the M x N output was written"
     buf = dev(torch.zeros((M, 3, N), dtype=td))       # output rows with a stride, untouched neighbours
     hip.gemv_w8(ad, qd, sd, dtype=dtype, out=buf[:, 1])
     _check(buf[:, 1], ref - b.double(), OUT_TOL[dtype], "w8 strided rows")
