@@ -1,9 +1,18 @@
-"""TEST-ONLY stand-in for ``stllm_amd.hip``: the same call surface implemented with plain fp32 torch ops on the CPU.
+"""TEST-ONLY stand-in for ``stllm_amd.hip``: the whole compute call surface of include/stllm_hip.h as plain torch on the CPU,
+every contract stated once.  It lets the product's *host code* (module graph, weight packers, index tables, KV caches, generate(),
+the training step, ``bench.py --dry-cpu``) run without a GPU.  It is NOT a fallback: nothing in ``st-llm_amd/`` imports it.
 
-Used by ``tests/test_host_orchestration_cpu.py`` to run the *product's host code* (module graph, weight packers,
-index tables, 2-level row indexing, frame-parallel + clip-parallel logic under gloo) without a GPU and compare it
-with the oracle.  It is NOT a fallback: nothing in ``st-llm_amd/`` imports it, and it lives under ``tests/``.
-Every function restates the contract documented in include/stllm_hip.h (incl. the packed weight layouts)."""
+Entry points, by the section of include/stllm_hip.h they restate:
+  GEMM family      gemm (stllm_gemm, a_norm_*, the packed weight layouts), gemv_w8 (stllm_gemv_w8), gemv_q4 (stllm_gemv_q4),
+                   lora_down (stllm_lora_down); one epilogue (_epilogue) and one fused-RMSNorm operand (_norm_operand) behind all of them
+  norms            layernorm, rmsnorm (stllm_rmsnorm, into a caller's strided rows with out_t)
+  attention        attention (stllm_attention, stllm_attention_offset with q_off; Sq = 1 with kv_len: the live keys only),
+                   attention_decode_ragged, attention_shared, kv_append_rows
+  rows / losses    gather_rows, mean_t, vit_cls_rows, cosine_rows, cross_entropy_rows, cast_rows, preprocess_frames
+  backward / opt   transpose .. sumsq ("backward / optimizer")
+  stacks           vit_blocks, llama_layers (stllm_llama_layers, stllm_llama_layers_lora), llama_layers_extend, qformer_layers: these
+                   run the product's per-op bodies, which call back through ``hip``; every other function calls its helpers directly.
+installed() patches all of them; counting() records the COUNTED names into CALLS; CALLS_W8 / CALLS_Q4 record the quantised GEMVs."""
 import contextlib
 import math
 
@@ -28,13 +37,61 @@ def _rows(t, n, rows):
     return (m // rpb) * (bs // t.stride(-2)) + (m % rpb)
 
 
+def _pairs(x, M, N):
+    """[M, N] as [M, N/64, 2, 32]: every 64-column group holds gate | up (SwiGLU) or the rotary halves x1 | x2 of half a head"""
+    return x.view(M, N // 64, 2, 32)
+
+
+def _rope_tables(cos, sin, M, N, rope_seq, rope_cols):
+    """(c, s, live) for the _pairs view: row m sits at position m % rope_seq; groups at columns >= rope_cols pass through"""
+    grp = torch.arange(N // 64)
+    pos = torch.arange(M) % rope_seq
+    fi = (grp % 2)[:, None] * 32 + torch.arange(32)[None, :]             # [groups, 32]
+    return cos[pos][:, fi], sin[pos][:, fi], (grp * 64 < rope_cols)[None, :, None]   # [M, groups, 32] x 2
+
+
+def _norm_operand(a, a_norm, dtype, max_rows):
+    """the fused RMSNorm operand of the decode regime (stllm_hip.h: a_norm_*): a = RMSNorm(xn) rounded to the compute dtype, for at most
+    max_rows rows (8 for the GEMM, 2 for the GEMVs)"""
+    if a_norm is None:
+        return a
+    xn, gamma, eps = a_norm
+    assert a is None and xn.shape[0] <= max_rows and torch_dtype(dtype) != torch.float32
+    return rmsnorm(xn, gamma, eps, dtype=dtype)[0]
+
+
+def _epilogue(acc, M, N, *, epilogue, td, act=ACT_NONE, resid=None, rope=None, rope_seq=0, rope_cols=0, out=None, out_f32=False, o_rows=None):
+    """what follows the fp32 accumulator (bias added) of gemm / gemv_w8 / gemv_q4: RESID | SWIGLU | ROPE | act + store"""
+    if epilogue == EPI_RESID:
+        res = resid[:M].float() + acc
+        dst = resid if out is None else out
+        dst[_rows(dst, M, o_rows)] = res
+        return dst
+    if epilogue == EPI_SWIGLU:
+        g = _pairs(acc, M, N)
+        val = (F.silu(g[:, :, 0]) * g[:, :, 1]).reshape(M, N // 2)
+    elif epilogue == EPI_ROPE:
+        x = _pairs(acc, M, N)
+        c, s, live = _rope_tables(*rope, M, N, rope_seq, rope_cols)
+        x1, x2 = x[:, :, 0], x[:, :, 1]
+        val = torch.stack((torch.where(live, x1 * c - x2 * s, x1), torch.where(live, x2 * c + x1 * s, x2)), dim=2).reshape(M, N)
+    else:
+        val = acc
+        if act == ACT_GELU:
+            val = 0.5 * val * (1.0 + torch.erf(val / math.sqrt(2.0)))
+        elif act == ACT_RELU:
+            val = torch.relu(val)
+    odt = torch.float32 if (out_f32 and epilogue == EPI_STORE) else td
+    if out is None:
+        return val.to(odt)
+    out[_rows(out, M, o_rows)] = val.to(out.dtype)
+    return out
+
+
 def gemm(a, w, *, dtype, epilogue=EPI_STORE, bias=None, out=None, out_f32=False, act=ACT_NONE, resid=None,
          rope=None, rope_seq=0, rope_cols=0, frames=None, pos_embed=None, n_frames=0, M=None, a_rows=None, o_rows=None, a_norm=None):
     td = torch_dtype(dtype)
-    if a_norm is not None:   # fused RMSNorm operand of the decode regime (stllm_hip.h: a_norm_*)
-        xn, gamma, eps = a_norm
-        assert a is None and xn.shape[0] <= 8 and td != torch.float32
-        a = rmsnorm(xn, gamma, eps, dtype=dtype)[0]
+    a = _norm_operand(a, a_norm, dtype, 8)
     wf = w.float()
     N = w.shape[0]
     if epilogue == EPI_PATCH:
@@ -57,36 +114,67 @@ def gemm(a, w, *, dtype, epilogue=EPI_STORE, bias=None, out=None, out_f32=False,
     acc = A @ wf.t()
     if bias is not None:
         acc = acc + bias
-    if epilogue == EPI_RESID:
-        res = resid[:M].float() + acc
-        dst = resid if out is None else out
-        dst[_rows(dst, M, o_rows)] = res
-        return dst
-    if epilogue == EPI_SWIGLU:
-        g = acc.view(M, N // 64, 2, 32)
-        val = (F.silu(g[:, :, 0]) * g[:, :, 1]).reshape(M, N // 2)
-    elif epilogue == EPI_ROPE:
-        cos, sin = rope
-        x = acc.view(M, N // 64, 2, 32).clone()
-        grp = torch.arange(N // 64)
-        pos = torch.arange(M) % rope_seq
-        fi = (grp % 2)[:, None] * 32 + torch.arange(32)[None, :]             # [groups, 32]
-        c, s = cos[pos][:, fi], sin[pos][:, fi]                                # [M, groups, 32]
-        live = (grp * 64 < rope_cols)[None, :, None]
-        x1, x2 = x[:, :, 0], x[:, :, 1]
-        y1 = torch.where(live, x1 * c - x2 * s, x1)
-        y2 = torch.where(live, x2 * c + x1 * s, x2)
-        val = torch.stack((y1, y2), dim=2).reshape(M, N)
-    else:
-        val = acc
-        if act == ACT_GELU:
-            val = 0.5 * val * (1.0 + torch.erf(val / math.sqrt(2.0)))
-        elif act == ACT_RELU:
-            val = torch.relu(val)
-    odt = torch.float32 if (out_f32 and epilogue == EPI_STORE) else td
-    if out is None:
-        return val.to(odt)
-    out[_rows(out, M, o_rows)] = val.to(out.dtype)
+    return _epilogue(acc, M, N, epilogue=epilogue, td=td, act=act, resid=resid, rope=rope, rope_seq=rope_seq, rope_cols=rope_cols,
+                     out=out, out_f32=out_f32, o_rows=o_rows)
+
+
+CALLS_W8, CALLS_Q4 = [], []   # (epilogue, M, N, K, fused_norm) of every gemv_w8 / gemv_q4 call since the last clear()
+
+
+def gemv_w8(a, wq, scale, *, dtype, epilogue=EPI_STORE, bias=None, resid=None, rope=None, rope_seq=0, rope_cols=0, out=None, out_f32=False,
+            a_norm=None, M=None, a_rows=None, o_rows=None):
+    """stllm_gemv_w8: epilogue(scale[n] * (A @ Wq^T) + bias), the scale applied to the finished sum"""
+    td = torch_dtype(dtype)
+    assert td in (torch.bfloat16, torch.float16) and wq.dtype == torch.int8 and scale.dtype == torch.float32
+    assert int(wq.abs().max()) <= 127 and epilogue in (EPI_STORE, EPI_RESID, EPI_SWIGLU, EPI_ROPE)
+    a = _norm_operand(a, a_norm, dtype, 2)
+    assert a.dtype == td and a_rows is None
+    M = a.shape[0] if M is None else M
+    N, K = wq.shape
+    assert M <= 16 and N % 64 == 0 and K % 16 == 0 and a.shape[-1] == K
+    CALLS_W8.append((epilogue, M, N, K, a_norm is not None))
+    acc = (a[:M].float() @ wq.float().t()) * scale[None, :]
+    if bias is not None:
+        acc = acc + bias
+    return _epilogue(acc, M, N, epilogue=epilogue, td=td, resid=resid, rope=rope, rope_seq=rope_seq, rope_cols=rope_cols,
+                     out=out, out_f32=out_f32, o_rows=o_rows)
+
+
+def gemv_q4(a, qp, scale, *, dtype, epilogue=EPI_STORE, bias=None, resid=None, rope=None, rope_seq=0, rope_cols=0, out=None, out_f32=False,
+            a_norm=None, M=None, a_rows=None, o_rows=None):
+    """stllm_gemv_q4: epilogue(sum_g scale[n, g] * (A[:, g] @ q[n, g]^T) + bias), the scale applied per 128-element K group; q comes from
+    pack.dequant4_groups (only pack.py and the kernel know the nibble placement)"""
+    from stllm_amd import pack
+    td = torch_dtype(dtype)
+    assert td in (torch.bfloat16, torch.float16) and qp.dtype == torch.uint8 and scale.dtype == torch.float32
+    assert epilogue in (EPI_STORE, EPI_RESID, EPI_SWIGLU, EPI_ROPE)
+    a = _norm_operand(a, a_norm, dtype, 2)
+    assert a.dtype == td and a_rows is None
+    M = a.shape[0] if M is None else M
+    N, K = qp.shape[0], qp.shape[1] * 2
+    assert M <= 16 and N % 64 == 0 and K % 128 == 0 and a.shape[-1] == K and tuple(scale.shape) == (N, K // 128)
+    q, _ = pack.dequant4_groups(qp, scale)
+    assert int(q.min()) >= -7 and int(q.max()) <= 7
+    CALLS_Q4.append((epilogue, M, N, K, a_norm is not None))
+    # sum_g scale[n, g] * (A_g @ q_g^T) as ONE fp32 product with the weight the format stands for, w = q * scale (one fp32 rounding per weight): the
+    # arithmetic of the 16-bit gemm above over that w, so the model tests compare routing and layouts, not two fp32 summation orders — whose
+    # 1e-7 differences flip a bf16 rounding of a hidden element now and then (measured: 3e-4 .. 1.7e-3 x logits per flip, int8 backend alike).  The
+    # order of the kernels' sums is the business of the emulator / GPU tests, against fp64.
+    w = (q.float().view(N, K // 128, 128) * scale[:, :, None]).reshape(N, K)
+    acc = a[:M].float() @ w.t()
+    if bias is not None:
+        acc = acc + bias
+    return _epilogue(acc, M, N, epilogue=epilogue, td=td, resid=resid, rope=rope, rope_seq=rope_seq, rope_cols=rope_cols,
+                     out=out, out_f32=out_f32, o_rows=o_rows)
+
+
+def lora_down(x, A, *, dtype, out, M=None):
+    """stllm_lora_down: out[:, :n] = x A^T (fp32 accumulation, rounded to the compute dtype), out[:, n:] = 0"""
+    M = x.shape[0] if M is None else M
+    n = A.shape[0]
+    assert n <= out.shape[1] <= 128 and out.shape[1] % 32 == 0 and x.shape[1] == A.shape[1]
+    out[:M, :n] = (x[:M].float() @ A.float().t()).to(out.dtype)
+    out[:M, n:] = 0
     return out
 
 
@@ -96,25 +184,110 @@ def layernorm(x, gamma, beta, eps, *, dtype, out_t=None, out_f32=None, want_t=Tr
 
 
 def rmsnorm(x, gamma, eps, *, dtype, out_t=None, out_f32=None, want_t=True, want_f32=False):
+    """stllm_rmsnorm; out_t: a caller's (strided) output rows — the K-extended QKV operand is one"""
     xf = x.float()
     y = gamma.float() * (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps))
-    return (y.to(torch_dtype(dtype)) if want_t else None), (y if want_f32 else None)
+    y_t = y.to(torch_dtype(dtype)) if want_t or out_t is not None else None
+    if out_t is not None:
+        out_t.copy_(y_t)
+        y_t = out_t
+    return y_t, (y if want_f32 else None)
+
+
+def _heads(t, B, S, H, D, strides):
+    """[B, S, H, D] view: element (b, s, h, d) lives at t.flat[b * batch_stride + s * row_stride + h * D + d] (include/stllm_hip.h)"""
+    bs, rs = strides if strides is not None else (S * t.stride(0), t.stride(0))
+    return torch.as_strided(t, (B, S, H, D), (bs, rs, D, 1), t.storage_offset())
+
+
+def _dead_keys(s, Skv, kv_len):
+    """scores with the keys at [kv_len[b], Skv) of batch row b at -inf: read, weightless, must be finite"""
+    if kv_len is None:
+        return s
+    dead = torch.arange(Skv)[None, :] >= kv_len.long()[:, None]
+    return s.masked_fill(dead[:, None, None, :], float("-inf"))
+
+
+def _causal_mask(Sq, Skv, q_off=0):
+    """True where key j is hidden from query row i, which sits at position q_off + i: j > q_off + i"""
+    return torch.arange(Skv)[None, :] > torch.arange(Sq)[:, None] + q_off
+
+
+def _attention_dense(q, k, v, *, B, H, Sq, Skv, D, scale, causal, kv_len, q_strides, k_strides, v_strides, q_off):
+    """the dense masked softmax: rows in [kv_len, Skv) are read, weightless, and must be finite (a NaN there reaches the output)"""
+    assert q_off >= 0 and (not q_off or q_off + Sq <= Skv)
+    qh, kh, vh = (_heads(t, B, S, H, D, st).float().transpose(1, 2) for t, S, st in ((q, Sq, q_strides), (k, Skv, k_strides), (v, Skv, v_strides)))
+    s = (qh @ kh.transpose(-1, -2)) * scale
+    if causal:
+        s = s.masked_fill(_causal_mask(Sq, Skv, q_off), float("-inf"))
+    return (_dead_keys(s, Skv, kv_len).softmax(-1) @ vh).transpose(1, 2).reshape(B * Sq, H * D).to(q.dtype)
 
 
 def attention(q, k, v, *, B, H, Sq, Skv, D, scale, causal=False, kv_len=None, out=None, q_strides=None, k_strides=None,
-              v_strides=None):
-    def heads(t, S, strides):
-        """element (b, s, h, d) lives at t.flat[b * batch_stride + s * row_stride + h * D + d] (include/stllm_hip.h)"""
-        bs, rs = strides if strides is not None else (S * t.stride(0), t.stride(0))
-        return torch.as_strided(t, (B, S, H, D), (bs, rs, D, 1), t.storage_offset()).float().transpose(1, 2)
-    qh, kh, vh = heads(q, Sq, q_strides), heads(k, Skv, k_strides), heads(v, Skv, v_strides)
-    s = (qh @ kh.transpose(-1, -2)) * scale
-    if causal:
-        s = s.masked_fill(torch.ones(Sq, Skv).triu(1).bool(), float("-inf"))
-    if kv_len is not None:
-        dead = torch.arange(Skv)[None, :] >= kv_len.long()[:, None]
-        s = s.masked_fill(dead[:, None, None, :], float("-inf"))
-    o = (s.softmax(-1) @ vh).transpose(1, 2).reshape(B * Sq, H * D).to(q.dtype)
+              v_strides=None, q_off=0):
+    """stllm_attention / stllm_attention_offset: query row i sits at position q_off + i; causal: key j visible iff j <= q_off + i.  The one-token
+    step over a ragged cache (Sq = 1 with kv_len) reads the LIVE keys of every row only, as the kernels do: the rows behind a row's length are
+    uninitialised memory, and 0 * NaN in a dense masked softmax would leak it.  Every other case is that dense masked softmax."""
+    if Sq == 1 and kv_len is not None:   # dead rows zeroed in a copy; a row of length <= 0 gets zeros
+        n = kv_len.clamp(max=Skv).long()
+        dead = torch.arange(Skv)[None, :] >= n[:, None]
+        kc, vc = (_heads(t, B, Skv, 1, H * D, st).squeeze(2).clone() for t, st in ((k, k_strides), (v, v_strides)))
+        kc[dead] = 0
+        vc[dead] = 0
+        o = _attention_dense(q, kc.view(B * Skv, H * D), vc.view(B * Skv, H * D), B=B, H=H, Sq=1, Skv=Skv, D=D, scale=scale, causal=False,
+                             kv_len=n.clamp(min=1), q_strides=q_strides, k_strides=None, v_strides=None, q_off=0)
+        o[n <= 0] = 0
+    else:
+        o = _attention_dense(q, k, v, B=B, H=H, Sq=Sq, Skv=Skv, D=D, scale=scale, causal=causal, kv_len=kv_len, q_strides=q_strides,
+                             k_strides=k_strides, v_strides=v_strides, q_off=q_off)
+    if out is not None:
+        out.copy_(o)
+        return out
+    return o
+
+
+def attention_decode_ragged(q, k, v, kv_len, *, B, H, max_kv, D, scale, out=None, q_stride=None, k_strides=None, v_strides=None):
+    """stllm_attention_decode_ragged: row b attends keys [0, min(kv_len[b], max_kv)); a row of length <= 0 gets zeros"""
+    return attention(q, k, v, B=B, H=H, Sq=1, Skv=max_kv, D=D, scale=scale, kv_len=kv_len, out=out,
+                     q_strides=(q.stride(0) if q_stride is None else q_stride,) * 2, k_strides=k_strides, v_strides=v_strides)
+
+
+def kv_append_rows(src, cache, pos, *, with_q=False):
+    """cache[b, pos[b], cols] = src[b, cols], cols = [k | v] (with_q: [q | k | v]); a position outside [0, max_len) is a free slot: nothing written"""
+    B, max_len, D3 = cache.shape
+    assert src.shape == (B, D3) and src.dtype == cache.dtype and pos.dtype == torch.int32 and pos.numel() == B
+    c0 = 0 if with_q else D3 // 3
+    for b, p in enumerate(pos.tolist()):
+        if 0 <= p < max_len:
+            cache[b, p, c0:] = src[b, c0:]
+    return cache
+
+
+def attention_shared(q, kp, vp, ks, vs, *, B, G, H, Sq, P, D, scale, max_sfx, sfx_len=None, sfx_q_off=0, causal=False, out=None,
+                     q_strides=None, kp_strides=None, ks_strides=None):
+    """stllm_attention_shared: fp64 softmax over the concatenated LIVE keys of every query row (the rows behind P and behind a row's suffix length
+    are uninitialised memory and are never read)"""
+    assert B % G == 0 and P > 0 and max_sfx > 0
+    R = B // G
+    qs = q_strides if q_strides is not None else (Sq * q.stride(0), q.stride(0))
+    kps = kp_strides if kp_strides is not None else (P * kp.stride(0), kp.stride(0))
+    kss = ks_strides if ks_strides is not None else (max_sfx * ks.stride(0), ks.stride(0))
+    lens = [max_sfx] * B if sfx_len is None else [min(int(n), max_sfx) for n in sfx_len.tolist()]
+
+    def rows(t, b, n, st):   # the first n rows of batch entry b: [n, H, D]
+        return torch.as_strided(t, (n, H, D), (st[1], D, 1), t.storage_offset() + b * st[0]).double()
+    o = torch.zeros((B * Sq, H * D), dtype=torch.float64)
+    for b in range(B):
+        g = b // R
+        kpre, vpre = rows(kp, g, P, kps), rows(vp, g, P, kps)
+        qb = rows(q, b, Sq, qs)
+        for i in range(Sq):
+            n = min(lens[b], sfx_q_off + i + 1) if causal else lens[b]
+            k = torch.cat([kpre, rows(ks, b, n, kss)]).transpose(0, 1)      # [H, P + n, D]
+            v = torch.cat([vpre, rows(vs, b, n, kss)]).transpose(0, 1)
+            s = (qb[i].unsqueeze(1) @ k.transpose(-1, -2)) * scale
+            o[b * Sq + i] = (s.softmax(-1) @ v).reshape(H * D)
+    o = o.to(q.dtype)
     if out is not None:
         out.copy_(o)
         return out
@@ -216,13 +389,13 @@ def layernorm_bwd(x, gamma, eps, dy, dx=None, *, accumulate=False):
 
 def swiglu(gu, out=None):
     M, N2 = gu.shape
-    g = gu.float().view(M, N2 // 64, 2, 32)
+    g = _pairs(gu.float(), M, N2)
     return (F.silu(g[:, :, 0]) * g[:, :, 1]).reshape(M, N2 // 2).to(gu.dtype)
 
 
 def swiglu_bwd(gu, dg, out=None):
     M, N2 = gu.shape
-    g = gu.float().view(M, N2 // 64, 2, 32)
+    g = _pairs(gu.float(), M, N2)
     gate, up = g[:, :, 0], g[:, :, 1]
     d = dg.float().view(M, N2 // 64, 32)
     sg = torch.sigmoid(gate)
@@ -233,12 +406,8 @@ def swiglu_bwd(gu, dg, out=None):
 
 def rope_bwd(dqkv, cos, sin, *, rope_seq, rope_cols):
     M, N = dqkv.shape
-    x = dqkv.float().view(M, N // 64, 2, 32)
-    grp = torch.arange(N // 64)
-    pos = torch.arange(M) % rope_seq
-    fi = (grp % 2)[:, None] * 32 + torch.arange(32)[None, :]
-    c, s = cos[pos][:, fi], sin[pos][:, fi]
-    live = (grp * 64 < rope_cols)[None, :, None]
+    x = _pairs(dqkv.float(), M, N)
+    c, s, live = _rope_tables(cos, sin, M, N, rope_seq, rope_cols)
     d1, d2 = x[:, :, 0], x[:, :, 1]
     x1 = torch.where(live, d1 * c + d2 * s, d1)
     x2 = torch.where(live, d2 * c - d1 * s, d2)
@@ -252,8 +421,7 @@ def attention_bwd(q, k, v, o, do, dq, dk, dv, *, B, H, S=None, D, scale, causal=
     Skv = S if Skv is None else Skv
 
     def heads(t, n, given):
-        bs, rs = given if given is not None else (n * t.stride(0), t.stride(0))
-        return torch.as_strided(t, (B, n, H, D), (bs, rs, D, 1), t.storage_offset())
+        return _heads(t, B, n, H, D, given)
     same = Sq == Skv
     ks = kv_strides if kv_strides is not None else (strides if same else None)
     dks = dkv_strides if dkv_strides is not None else (d_strides if same else None)
@@ -262,11 +430,8 @@ def attention_bwd(q, k, v, o, do, dq, dk, dv, *, B, H, S=None, D, scale, causal=
     doh = heads(do, Sq, do_strides).float().transpose(1, 2)
     s = (qh @ kh.transpose(-1, -2)) * scale
     if causal:
-        s = s.masked_fill(torch.ones(Sq, Skv).triu(1).bool(), float("-inf"))
-    if kv_len is not None:
-        dead = torch.arange(Skv)[None, :] >= kv_len.long()[:, None]
-        s = s.masked_fill(dead[:, None, None, :], float("-inf"))
-    p = s.softmax(-1)
+        s = s.masked_fill(_causal_mask(Sq, Skv), float("-inf"))
+    p = _dead_keys(s, Skv, kv_len).softmax(-1)
     gv = p.transpose(-1, -2) @ doh
     dp = doh @ vh.transpose(-1, -2)
     ds = p * (dp - (dp * p).sum(-1, keepdim=True))
@@ -372,15 +537,31 @@ def llama_layer_array(layers, cache=None):
     return None
 
 
-class _LM:   # the bits of LlamaModel that prefill_layers_per_op reads
+def llama_lora_array(layers):
+    return None
+
+
+class _LM:
+    """the bits of LlamaModel that the per-op bodies read: config, and the adapted layers' operand builder"""
     def __init__(self, hidden, n_heads, eps):
         import types
         self.config = types.SimpleNamespace(hidden_size=hidden, num_attention_heads=n_heads, rms_norm_eps=eps)
 
+    def qkv_operand(self, x, pk, dt):
+        from stllm_amd.models.llama import LlamaModel
+        return LlamaModel.qkv_operand(self, x, pk, dt)
 
-def llama_layers(x, layers, carr, *, B, S, n_heads, eps, rope, dtype, kv_len=None, cache=None):
+
+def llama_layers(x, layers, carr, *, B, S, n_heads, eps, rope, dtype, kv_len=None, cache=None, lora=None):
+    """stllm_llama_layers / stllm_llama_layers_lora: the per-op body (the adapters travel inside the packed layer dicts)"""
     from stllm_amd.models.llama import LlamaModel
     return LlamaModel.prefill_layers_per_op(_LM(x.shape[1], n_heads, eps), x, layers, B, S, rope[0], rope[1], kv_len, cache, dtype)
+
+
+def llama_layers_extend(x, layers, carr, *, B, S, pos0, n_heads, eps, rope, dtype, cache):
+    """stllm_llama_layers_extend: the per-op body (what the C entry point issues)"""
+    from stllm_amd.models.llama import LlamaModel
+    return LlamaModel.extend_layers_per_op(_LM(x.shape[1], n_heads, eps), x, layers, B, S, pos0, rope[0], rope[1], cache, dtype)
 
 
 def qformer_layer_array(layers):
@@ -395,20 +576,45 @@ def qformer_layers(hq32, hq16, ht32, ht16, enc16, layers, carr, *, n_seq, n_quer
     return BertModel.encode_layers_per_op(shim, layers, hq32, hq16, ht32, ht16, enc16, n_seq, n_query, n_text, kv_len, dtype)
 
 
+NAMES = ["gemm", "gemv_w8", "gemv_q4", "lora_down", "layernorm", "rmsnorm", "attention", "attention_decode_ragged", "attention_shared",
+         "kv_append_rows", "gather_rows", "mean_t", "vit_cls_rows", "cosine_rows", "cross_entropy_rows", "cast_rows", "preprocess_frames",
+         "transpose", "rmsnorm_bwd", "layernorm_bwd", "swiglu", "swiglu_bwd", "rope_bwd", "attention_bwd", "cross_entropy_bwd",
+         "scatter_add_rows", "cosine_rows_bwd", "colsum", "relu_bwd", "gelu", "gelu_bwd", "scale_rows", "bcast_add_t", "adamw", "sumsq",
+         "vit_block_array", "vit_blocks", "llama_layer_array", "llama_lora_array", "llama_layers", "llama_layers_extend",
+         "qformer_layer_array", "qformer_layers"]
+CALLS = []   # the name of every COUNTED entry point called while counting() is active
+COUNTED = ["gemm", "gemv_w8", "rmsnorm", "attention", "attention_decode_ragged", "kv_append_rows", "gather_rows", "lora_down", "attention_shared"]
+
+
 @contextlib.contextmanager
-def installed():
-    """Monkey-patch stllm_amd.hip's compute entry points with the functions above (tests only)."""
+def _patched(fns):
+    """stllm_amd.hip with the entry points {name: function} swapped in; whatever was there before comes back on exit, so nesting is harmless"""
     from stllm_amd import hip
-    names = ["gemm", "layernorm", "rmsnorm", "attention", "gather_rows", "mean_t", "vit_cls_rows", "cosine_rows",
-             "cross_entropy_rows", "cast_rows", "preprocess_frames", "transpose", "rmsnorm_bwd", "layernorm_bwd", "swiglu",
-             "swiglu_bwd", "rope_bwd", "attention_bwd", "cross_entropy_bwd", "scatter_add_rows", "cosine_rows_bwd", "colsum",
-             "relu_bwd", "gelu", "gelu_bwd", "scale_rows", "bcast_add_t", "adamw", "sumsq", "vit_block_array", "vit_blocks",
-             "llama_layer_array", "llama_layers", "qformer_layer_array", "qformer_layers"]
-    saved = {n: getattr(hip, n) for n in names}
+    saved = {n: getattr(hip, n) for n in fns}
     try:
-        for n in names:
-            setattr(hip, n, globals()[n])
+        for n, f in fns.items():
+            setattr(hip, n, f)
         yield
     finally:
         for n, f in saved.items():
             setattr(hip, n, f)
+
+
+def installed():
+    """Monkey-patch stllm_amd.hip's compute entry points with the functions above (tests only)."""
+    return _patched({n: globals()[n] for n in NAMES})
+
+
+@contextlib.contextmanager
+def counting():
+    """inside installed(): append the name of every COUNTED entry point that the host code calls to CALLS"""
+    from stllm_amd import hip
+
+    def wrap(name, f):
+        def g(*a, **k):
+            CALLS.append(name)
+            return f(*a, **k)
+        return g
+    CALLS.clear()
+    with _patched({n: wrap(n, getattr(hip, n)) for n in COUNTED}):
+        yield CALLS

@@ -49,3 +49,33 @@ def assert_close(got, want, atol, rtol=0.0, what=""):
     bad = err > tol
     assert not bad.any(), (f"{what}: {bad.sum()}/{bad.size} elements out of tolerance; max err {err.max():.3e} "
                            f"(atol {atol}, rtol {rtol}); ref abs-max {np.abs(want).max():.3e}")
+
+
+def small_llama(cfg, r=0, lm_head_spread=None):
+    """a synth-filled STLLMForCausalLM(StllmConfig(**cfg)) on the CPU.  r: LoRA adapters of that rank with a non-zero B;
+    lm_head_spread: a factor on the lm_head that spreads the logits so that the rows of a batch take different paths"""
+    from stllm_amd.models.st_llm import STLLMForCausalLM, StllmConfig
+    m = STLLMForCausalLM(StllmConfig(**cfg), device="cpu")
+    synth.fill_module_(m, 0, "")
+    if lm_head_spread is not None:
+        m.lm_head.weight.mul_(lm_head_spread)
+    if r:
+        m.add_lora(r, 32)
+        for i, mod in enumerate(m._lora_modules()):
+            mod.B.copy_(T(f"ragged.B{i}", tuple(mod.B.shape), 0.05))
+    return m
+
+
+def decode_run(model, emb, S, n_new, before_decode=None):
+    """prefill S positions, then n_new decode steps: the logits of every step"""
+    lm = model.model
+    B = emb.shape[0]
+    c = lm.new_cache(B, S + n_new + 2, "cpu")
+    lm.prefill(emb[:, :S], None, cache=c)
+    if before_decode is not None:
+        before_decode()
+    out = []
+    for t in range(n_new):
+        _, h = lm.decode_step(emb[:, S + t:S + t + 1], c)
+        out.append(model.logits_from(h, B, 1)[:, 0].clone())
+    return out

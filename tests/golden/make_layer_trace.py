@@ -1,4 +1,4 @@
-"""Call trace of the Llama decoder-layer host paths (models/llama.py) on the stacked CPU contract backend (tests/_cpu_backend_q4.py).
+"""Call trace of the Llama decoder-layer host paths (models/llama.py) on the CPU contract backend (tests/_cpu_backend.py).
 
     python tests/golden/make_layer_trace.py      -> tests/golden/llama_layer_trace.json
 
@@ -159,7 +159,7 @@ def mask_of(lens, S):
 
 def record():
     """{case: [entry, ...]} for every case; the set-up of a case (the prefill in front of a decode step, ...) is not traced"""
-    import _cpu_backend_q4 as CB
+    import _cpu_backend as CB
     from stllm_amd import runtime
     from stllm_amd.models import llama
     out = {}

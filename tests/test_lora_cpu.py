@@ -1,12 +1,12 @@
 """CPU: the host side of the LoRA adapters (models/lora.py, LlamaModel with active adapters, checkpoint key layouts, rejections) on the
-test-only contract backend (tests/_cpu_backend_lora.py), against the reference-pinned oracle fed with `W + s·B·A` (fp64) as a plain weight.
+test-only contract backend (tests/_cpu_backend.py), against the reference-pinned oracle fed with `W + s·B·A` (fp64) as a plain weight.
 peft is not available: there is no reference fixture for this branch."""
 import os
 
 import pytest
 import torch
 
-import _cpu_backend_lora as CB
+import _cpu_backend as CB
 import stllm_oracle as O
 from _util import T
 

@@ -4,7 +4,7 @@ Tolerance: 2e-4 of each tensor's abs-max (the CPU backward bound of the issue; t
 import pytest
 import torch
 
-import _cpu_backend_lora as CB
+import _cpu_backend as CB
 import _lora_train_case as C
 
 torch.set_grad_enabled(False)

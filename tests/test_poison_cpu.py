@@ -1,4 +1,4 @@
-"""CPU: poisoned-allocation runs (tests/_poison.py) of the product's HOST code on the test-only contract backends (tests/_cpu_backend*.py).
+"""CPU: poisoned-allocation runs (tests/_poison.py) of the product's HOST code on the test-only contract backend (tests/_cpu_backend.py).
 Every path runs twice clean (A, B) and once with every torch.empty / empty_like / empty_strided / new_empty result, every hand-out of the persistent
 scratch and every truncated cache row filled with 0xFF (P).  On the DEFINED outputs: A == B and P == A bit for bit, P finite, poison count > 0.
 The positive controls show that the comparison flags the three ways a result can depend on unwritten memory.  (The kernels' side of the same
@@ -8,10 +8,10 @@ import contextlib
 import pytest
 import torch
 
-import _cpu_backend_q4 as CB          # the whole chain: base + LoRA + prefix + int8 + ragged + shared + int4
+import _cpu_backend as CB
 import _poison
 from _poison import compare, poisoned_allocations
-from _util import T
+from _util import T, small_llama
 
 torch.set_grad_enabled(False)
 
@@ -176,27 +176,14 @@ def test_a_path_that_poisons_nothing_fails_the_count():
 SMALL = dict(num_hidden_layers=2, hidden_size=256, intermediate_size=768, num_attention_heads=2, vocab_size=512)   # tests/test_q4_cpu.py: both K % 128 == 0
 
 
-def _small(r=0):
-    from stllm_amd import synth
-    from stllm_amd.models.st_llm import STLLMForCausalLM, StllmConfig
-    m = STLLMForCausalLM(StllmConfig(**SMALL), device="cpu")
-    synth.fill_module_(m, 0, "")
-    m.lm_head.weight.mul_(6.0)   # as tests/test_ragged_cpu.py: spread the logits so that the rows take different paths
-    if r:
-        m.add_lora(r, 32)
-        for i, mod in enumerate(m._lora_modules()):
-            mod.B.copy_(T(f"ragged.B{i}", tuple(mod.B.shape), 0.05))
-    return m
-
-
 @pytest.fixture(scope="module")
 def small():
-    return _small()
+    return small_llama(SMALL, lm_head_spread=6.0)   # as tests/test_ragged_cpu.py: the rows take different paths
 
 
 @pytest.fixture(scope="module")
 def small_lora():
-    return _small(r=8)
+    return small_llama(SMALL, r=8, lm_head_spread=6.0)
 
 
 EMB = lambda: T("poison.emb", (4, 40, 256), 0.05)

@@ -1,5 +1,5 @@
 """CPU: the prefix KV cache — attention with a query offset, LlamaModel.extend, KVCache.fork / truncate, generate(prefix_cache=...), Chat.prefill_video /
-answer(prefix=...) — on the test-only contract backend (tests/_cpu_backend_prefix.py, fp32), plus the offset attention kernels themselves on the host
+answer(prefix=...) — on the test-only contract backend (tests/_cpu_backend.py, fp32), plus the offset attention kernels themselves on the host
 emulator (tests/hipemu) and the C ABI surface."""
 import os
 import re
@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-import _cpu_backend_prefix as CB
+import _cpu_backend as CB
 import _hipemu
 from _util import T, golden
 

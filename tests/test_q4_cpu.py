@@ -1,6 +1,6 @@
 """CPU: int4 weight-only decode (W4A16, group-scaled) — the quantiser (pack.quant4_groups / dequant4_groups), the kernels of stllm_gemv_q4 on the host
 emulator (tests/hipemu) against fp64 of the contract, LlamaModel.decode_step / generate under runtime.use_decode_weights("int4g128") on the test-only
-contract backend (tests/_cpu_backend_q4.py), and the C ABI surface."""
+contract backend (tests/_cpu_backend.py), and the C ABI surface."""
 import os
 import re
 
@@ -9,9 +9,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import _cpu_backend_prefix as CB0
+import _cpu_backend as CB
 import _hipemu
-from _util import T
+from _util import T, decode_run, small_llama
 from test_kernels_gpu import ACC_TOL, OUT_TOL   # the 16-bit GEMV's error model: the products a * q are exact
 from test_w8_cpu import EMU_CASES, rope_ref
 
@@ -214,67 +214,46 @@ def test_gemv_q4_kernels_emulated(dtype, N, K):
 
 
 # ---- model ----------------------------------------------------------------------------------------------------------------------
-def _small():
-    from stllm_amd import synth
-    from stllm_amd.models.st_llm import STLLMForCausalLM, StllmConfig
-    m = STLLMForCausalLM(StllmConfig(**SMALL), device="cpu")
-    synth.fill_module_(m, 0, "")
-    return m
-
-
-def _decode_run(model, emb, S, n_new, before_decode=None):
-    """prefill S positions, then n_new decode steps: the logits of every step"""
-    lm = model.model
-    B = emb.shape[0]
-    c = lm.new_cache(B, S + n_new + 2, "cpu")
-    lm.prefill(emb[:, :S], None, cache=c)
-    if before_decode is not None:
-        before_decode()
-    out = []
-    for t in range(n_new):
-        _, h = lm.decode_step(emb[:, S + t:S + t + 1], c)
-        out.append(model.logits_from(h, B, 1)[:, 0].clone())
-    return out
-
-
 @pytest.fixture(scope="module")
 def small():
-    return _small()
+    return small_llama(SMALL)
 
 
 @pytest.fixture(scope="module")
 def baseline(small):
-    """decode logits of the 16-bit path on the backend WITHOUT the quantised entry points"""
+    """decode logits of the 16-bit path before a quantised mode was ever switched on: no quantised entry point is reached"""
     from stllm_amd import runtime
     emb = T("q4.emb", (2, 12, 256), 0.05)
-    with CB0.installed(), runtime.use_dtype("bf16"):
-        return emb, _decode_run(small, emb, 8, 4)
+    with CB.installed(), runtime.use_dtype("bf16"):
+        CB.CALLS_W8.clear(); CB.CALLS_Q4.clear()
+        base16 = decode_run(small, emb, 8, 4)
+        assert CB.CALLS_W8 == [] and CB.CALLS_Q4 == []
+        return emb, base16
 
 
 def test_int4_decode_equals_the_dequantised_model(small, baseline):
-    import _cpu_backend_q4 as CB
     from stllm_amd import pack, runtime
     emb, base16 = baseline
     lm = small.model
     with CB.installed(), runtime.use_dtype("bf16"):
-        CB.CALLS.clear()
+        CB.CALLS_Q4.clear()
         with runtime.use_decode_weights("int4g128"):
-            got = _decode_run(small, emb, 8, 4)
-        assert len(CB.CALLS) == 4 * 2 * 4 and all(c[1] == 2 for c in CB.CALLS), "4 projections per layer and step"
-        assert sum(c[4] for c in CB.CALLS) == 4 * 2 * 2, "B = 2 <= FUSE_NORM_ROWS: the qkv and gate/up projections take the fused-norm form"
+            got = decode_run(small, emb, 8, 4)
+        assert len(CB.CALLS_Q4) == 4 * 2 * 4 and all(c[1] == 2 for c in CB.CALLS_Q4), "4 projections per layer and step"
+        assert sum(c[4] for c in CB.CALLS_Q4) == 4 * 2 * 2, "B = 2 <= FUSE_NORM_ROWS: the qkv and gate/up projections take the fused-norm form"
         assert runtime.decode_weights() is None
 
         def dequantise():   # the SAME 16-bit decode path over q * scale (fp32 tensors in place of the packed weights; the prefill before it used the originals)
             for pk in lm.pack(torch.bfloat16):
                 for k in Q4_KEYS:
                     pk[k] = deq(*pack.quant4_groups(pk[k])).float()
-        CB.CALLS.clear()
+        CB.CALLS_Q4.clear()
         try:
-            want = _decode_run(small, emb, 8, 4, before_decode=dequantise)
+            want = decode_run(small, emb, 8, 4, before_decode=dequantise)
         finally:
             lm.repack()
-        assert CB.CALLS == []
-        again = _decode_run(small, emb, 8, 4)   # mode None (the default): bit-identical to the run made before the mode was ever switched on
+        assert CB.CALLS_Q4 == []
+        again = decode_run(small, emb, 8, 4)   # mode None (the default): bit-identical to the run made before the mode was ever switched on
     scale = max(float(w.abs().max()) for w in want)
     for g, w in zip(got, want):
         assert float((g - w).abs().max()) <= TOL * scale, (float((g - w).abs().max()), scale)
@@ -284,8 +263,6 @@ def test_int4_decode_equals_the_dequantised_model(small, baseline):
 
 def test_int4_weight_cache_follows_the_parameters_and_the_mode(small):
     """the 4-bit copy is keyed by the parameter fingerprint like the int8 one; one quantised copy at a time: int8 <-> int4g128 frees the other at the next step"""
-    import _cpu_backend_q4 as CB
-    import _cpu_backend_w8 as CB8
     from stllm_amd import runtime
     lm = small.model
     emb = T("q4.emb", (1, 6, 256), 0.05)
@@ -295,33 +272,33 @@ def test_int4_weight_cache_follows_the_parameters_and_the_mode(small):
         with CB.installed(), runtime.use_dtype("bf16"):
             runtime.set_decode_weights("int4g128")
             assert runtime.decode_weights() == "int4g128"
-            a = _decode_run(small, emb, 4, 2)
+            a = decode_run(small, emb, 4, 2)
             assert lm._quant[:2] == ("int4g128", torch.bfloat16)
             first = lm._quant.layers
             assert set(first[0]) == set(Q4_KEYS) and first[1]["wdown"][0].dtype == torch.uint8
             assert first[1]["wdown"][0].shape == (256, 384) and first[1]["wdown"][1].shape == (256, 6) and first[0]["wqkv"][1].shape == (768, 2)
-            _decode_run(small, emb, 4, 1)
+            decode_run(small, emb, 4, 1)
             assert lm._quant[:2] == ("int4g128", torch.bfloat16) and lm._quant.layers is first, "unchanged parameters: the cached copy"
             w.copy_(w0 * 1.5)
-            b = _decode_run(small, emb, 4, 2)
+            b = decode_run(small, emb, 4, 2)
             assert lm._quant[:2] == ("int4g128", torch.bfloat16)
             second = lm._quant.layers
             assert second is not first and not torch.equal(second[1]["wdown"][1], first[1]["wdown"][1])
             assert torch.equal(second[0]["wqkv"][0], first[0]["wqkv"][0]) and not torch.equal(a[-1], b[-1])
             assert lm._quant.mode != "int8", "no int8 copy is held"
             runtime.set_decode_weights("int8")
-            CB.CALLS.clear(); CB8.CALLS.clear()
-            _decode_run(small, emb, 4, 1)
-            assert lm._quant[:2] == ("int8", torch.bfloat16) and CB.CALLS == [] and len(CB8.CALLS) == 8, "int8: the 4-bit copy is freed"
+            CB.CALLS_Q4.clear(); CB.CALLS_W8.clear()
+            decode_run(small, emb, 4, 1)
+            assert lm._quant[:2] == ("int8", torch.bfloat16) and CB.CALLS_Q4 == [] and len(CB.CALLS_W8) == 8, "int8: the 4-bit copy is freed"
             runtime.set_decode_weights("int4g128")
-            CB8.CALLS.clear()
-            _decode_run(small, emb, 4, 1)
-            assert lm._quant[:2] == ("int4g128", torch.bfloat16) and len(CB.CALLS) == 8 and CB8.CALLS == [], "and back: the int8 copy is freed"
+            CB.CALLS_W8.clear()
+            decode_run(small, emb, 4, 1)
+            assert lm._quant[:2] == ("int4g128", torch.bfloat16) and len(CB.CALLS_Q4) == 8 and CB.CALLS_W8 == [], "and back: the int8 copy is freed"
             lm.repack()
             assert lm._quant is None
-            _decode_run(small, emb, 4, 1)
+            decode_run(small, emb, 4, 1)
             runtime.set_decode_weights(None)
-            _decode_run(small, emb, 4, 1)
+            decode_run(small, emb, 4, 1)
             assert lm._quant is None, "mode off: no quantised copy"
             for bad in ("int4", "int4g64", "q4"):
                 with pytest.raises(ValueError, match="int4g128"):
@@ -334,9 +311,8 @@ def test_int4_weight_cache_follows_the_parameters_and_the_mode(small):
 
 
 def test_int4_rejects_the_modes_it_does_not_serve():
-    import _cpu_backend_q4 as CB
     from stllm_amd import runtime
-    m = _small()
+    m = small_llama(SMALL)
     emb = T("q4.emb", (1, 6, 256), 0.05)
     with CB.installed(), runtime.use_decode_weights("int4g128"):
         with runtime.use_dtype("fp32"):
@@ -351,16 +327,15 @@ def test_int4_rejects_the_modes_it_does_not_serve():
             mod.B.copy_(T(f"q4.lora.B{i}", tuple(mod.B.shape), 0.02))
         with runtime.use_dtype("bf16"):
             with pytest.raises(NotImplementedError, match=r"int4g128 decode weights with active LoRA adapters: merge_adapter\(\) first"):
-                _decode_run(m, emb, 4, 1)
+                decode_run(m, emb, 4, 1)
             m.merge_adapter()
-            CB.CALLS.clear()
-            _decode_run(m, emb, 4, 1)
-            assert len(CB.CALLS) == 8
+            CB.CALLS_Q4.clear()
+            decode_run(m, emb, 4, 1)
+            assert len(CB.CALLS_Q4) == 8
 
 
 def test_generate_runs_through_the_int4_path(small):
     """greedy behind a prefix cache, 5 beams, batching="ragged" and share_prefix=True: every decode step makes 4 q4 calls per layer, the norms fused for <= 2 rows"""
-    import _cpu_backend_q4 as CB
     from stllm_amd import runtime
     emb = T("q4.gen", (1, 9, 256), 0.05)
     emb2 = T("q4.gen2", (2, 9, 256), 0.05)
@@ -369,10 +344,10 @@ def test_generate_runs_through_the_int4_path(small):
     shapes = ((768, 256), (256, 256), (1536, 256), (256, 768))
 
     def counted(rows, fused):
-        n = len(CB.CALLS)
+        n = len(CB.CALLS_Q4)
         assert n > 0 and n % 8 == 0, n
-        assert all(c[1] == rows and c[2:4] in shapes for c in CB.CALLS), sorted(set(CB.CALLS))
-        per_step = [CB.CALLS[i:i + 8] for i in range(0, n, 8)]
+        assert all(c[1] == rows and c[2:4] in shapes for c in CB.CALLS_Q4), sorted(set(CB.CALLS_Q4))
+        per_step = [CB.CALLS_Q4[i:i + 8] for i in range(0, n, 8)]
         assert all([c[2:4] for c in st] == list(shapes) * 2 for st in per_step), "qkv, o, gate/up, down per layer"
         assert all(sum(c[4] for c in st) == (4 if fused else 0) for st in per_step)
         return n
@@ -382,29 +357,29 @@ def test_generate_runs_through_the_int4_path(small):
         small.model.prefill(emb[:, :5], None, cache=prefix)
         before = [b.clone() for b in prefix.qkv]
         with runtime.use_decode_weights("int4g128"):
-            CB.CALLS.clear()
+            CB.CALLS_Q4.clear()
             ids = small.generate(inputs_embeds=emb[:, 5:], prefix_cache=prefix, num_beams=1, **kw)
             assert ids.shape == (1, 5) and int(ids.min()) >= 0 and int(ids.max()) < 512
             counted(1, True)
             assert prefix.len == 5 and all(torch.equal(x, y) for x, y in zip(prefix.qkv, before))
-            CB.CALLS.clear()
+            CB.CALLS_Q4.clear()
             ids5 = small.generate(inputs_embeds=emb, num_beams=5, **kw)
             assert ids5.shape[0] == 1 and int(ids5.min()) >= 0 and int(ids5.max()) < 512
             counted(5, False)
-            CB.CALLS.clear()
+            CB.CALLS_Q4.clear()
             idr = small.generate(inputs_embeds=emb2, attention_mask=mask2, batching="ragged", **kw)
             assert idr.shape[0] == 2
             counted(2, True)
-            CB.CALLS.clear()
+            CB.CALLS_Q4.clear()
             ids_s = small.generate(inputs_embeds=emb[:, 5:], prefix_cache=prefix, num_beams=5, share_prefix=True, **kw)
             assert ids_s.shape[0] == 1
             counted(5, False)
-            CB.CALLS.clear()
+            CB.CALLS_Q4.clear()
             ids_f = small.generate(inputs_embeds=emb[:, 5:], prefix_cache=prefix, num_beams=5, **kw)
             assert torch.equal(ids_s, ids_f), "shared base == forked copies under 4-bit weights"
             assert prefix.len == 5 and all(torch.equal(x, y) for x, y in zip(prefix.qkv, before))
-        CB.CALLS.clear()
-        assert torch.equal(small.generate(inputs_embeds=emb, num_beams=5, **kw), off) and CB.CALLS == []
+        CB.CALLS_Q4.clear()
+        assert torch.equal(small.generate(inputs_embeds=emb, num_beams=5, **kw), off) and CB.CALLS_Q4 == []
 
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """CPU: the ragged KV cache — decode attention with per-row lengths and the KV append scatter on the host emulator of the real sources (tests/hipemu),
 KVCache.lens, ragged prefill / extend / decode_step, generate(batching="ragged"), Chat.answer_many on the test-only contract backend
-(tests/_cpu_backend_ragged.py, fp32), and the C ABI surface."""
+(tests/_cpu_backend.py, fp32), and the C ABI surface."""
 import os
 import re
 
@@ -8,9 +8,9 @@ import numpy as np
 import pytest
 import torch
 
-import _cpu_backend_ragged as CB
+import _cpu_backend as CB
 import _hipemu
-from _util import T
+from _util import T, small_llama
 
 torch.set_grad_enabled(False)
 EMU_TOL = {torch.bfloat16: 2.0 ** -7, torch.float16: 2.0 ** -10}   # tests/test_kernels_emulated_cpu.py TOL: one rounding step of the 16-bit output
@@ -160,18 +160,6 @@ def _build(cfg, vit_depth=1, qf_layers=2, llm_layers=2):
 def stllm():
     m = _build(CFG)
     m.lm_head.weight.mul_(6.0)   # as test_generate_padded_batch_by_length_groups: spread the logits so that the rows take different paths
-    return m
-
-
-def _small(r=0):
-    from stllm_amd import synth
-    from stllm_amd.models.st_llm import STLLMForCausalLM, StllmConfig
-    m = STLLMForCausalLM(StllmConfig(**SMALL), device="cpu")
-    synth.fill_module_(m, 0, "")
-    if r:
-        m.add_lora(r, 32)
-        for i, mod in enumerate(m._lora_modules()):
-            mod.B.copy_(T(f"ragged.B{i}", tuple(mod.B.shape), 0.05))
     return m
 
 
@@ -343,7 +331,7 @@ def test_uniform_step_is_unchanged_and_ragged_step_adds_the_append():
     gathers of the step.  A ragged cache whose rows have one length gives the uniform step's logits bit for bit; different lengths give, per row, the
     logits of that row decoded alone."""
     from stllm_amd import runtime
-    model = _small()
+    model = small_llama(SMALL)
     lm = model.model
     emb = T("ragged.emb", (3, 12, 256), 0.05)
     lens = [8, 5, 3]
@@ -390,7 +378,7 @@ def test_ragged_step_under_int8_weights_and_lora_shares_the_attention_half(mode)
     adapters; with different lengths every row equals itself alone (one code path for the attention half: LlamaModel.decode_attn)"""
     import contextlib
     from stllm_amd import runtime
-    model = _small(r=8 if mode == "lora" else 0)
+    model = small_llama(SMALL, r=8 if mode == "lora" else 0)
     lm = model.model
     emb = T("ragged.emb", (2, 12, 256), 0.05)
     ctx = runtime.use_decode_weights("int8") if mode == "int8" else contextlib.nullcontext()

@@ -1,15 +1,15 @@
 """CPU: the shared-prefix KV cache — KVCache.share bookkeeping, decode steps / extend on a cache with a base against forked copies,
-generate(share_prefix=True) and Chat.answer_many(share_prefix=True) on the test-only contract backend (tests/_cpu_backend_shared.py, fp32), the entry
+generate(share_prefix=True) and Chat.answer_many(share_prefix=True) on the test-only contract backend (tests/_cpu_backend.py, fp32), the entry
 points a shared step calls, the error paths, and the new 16-bit decode kernels + merge executed from source by the host emulator (tests/hipemu)."""
 import numpy as np
 import pytest
 import torch
 
-import _cpu_backend_shared as CB
+import _cpu_backend as CB
 import _hipemu
 import _shared_case as SC
-from _util import T
-from test_ragged_cpu import CFG, UNIFORM_LAYER, _build, _padded, _small
+from _util import T, small_llama
+from test_ragged_cpu import CFG, SMALL, UNIFORM_LAYER, _build, _padded
 
 torch.set_grad_enabled(False)
 needs_emu = pytest.mark.skipif(not _hipemu.available() or _hipemu.ON_DEVICE, reason="ROCm clang++ not found: cannot build the emulated kernels")
@@ -35,7 +35,7 @@ def _logits(model, cache, toks):
 def test_share_bookkeeping():
     from stllm_amd import runtime
     from stllm_amd.models.llama import KVCache
-    model = _small()
+    model = small_llama(SMALL)
     lm = model.model
     emb = T("shared.emb", (2, 24, 256), 0.05)
     with CB.installed(), runtime.use_dtype("fp32"):
@@ -110,7 +110,7 @@ def test_shared_decode_steps_equal_forked_copies():
     """2 layers, P = 13, suffix lengths [5, 1, 5, 3], 6 steps: the logits on the shared cache equal those on a fork()ed (dense, private) copy to fp32
     round-off — the backend's attention_shared sums in fp64 over the concatenated keys, the copy path in fp32 over the same keys"""
     from stllm_amd import runtime
-    model = _small()
+    model = small_llama(SMALL)
     lm = model.model
     P, sfx, steps = 13, [5, 1, 5, 3], 6
     emb = T("shared.emb2", (4, 32, 256), 0.05)
@@ -200,7 +200,7 @@ def test_chat_answer_many_share_prefix(stllm):
 def test_shared_step_calls_attention_shared_once_per_layer(mode):
     import contextlib
     from stllm_amd import runtime
-    model = _small(r=8 if mode == "lora" else 0)
+    model = small_llama(SMALL, r=8 if mode == "lora" else 0)
     lm = model.model
     emb = T("ragged.emb", (3, 12, 256), 0.05)
     dt = "fp32" if mode == "plain" else "bf16"
@@ -231,7 +231,7 @@ def test_shared_step_calls_attention_shared_once_per_layer(mode):
 # ---- 6. error paths --------------------------------------------------------------------------------------------------------------------------------
 def test_shared_error_paths(stllm):
     from stllm_amd import runtime
-    model = _small()
+    model = small_llama(SMALL)
     lm = model.model
     emb = T("shared.emb", (2, 24, 256), 0.05)
     with CB.installed(), runtime.use_dtype("fp32"):

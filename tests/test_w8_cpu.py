@@ -1,6 +1,6 @@
 """CPU: int8 weight-only decode (W8A16) — the quantiser (pack.quant8_rows), the kernels of stllm_gemv_w8 on the host emulator (tests/hipemu)
 against fp64 of the contract, LlamaModel.decode_step / generate under runtime.use_decode_weights("int8") on the test-only contract backend
-(tests/_cpu_backend_w8.py), and the C ABI surface."""
+(tests/_cpu_backend.py), and the C ABI surface."""
 import os
 import re
 
@@ -9,9 +9,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import _cpu_backend_prefix as CB0
+import _cpu_backend as CB
 import _hipemu
-from _util import T
+from _util import T, decode_run, small_llama
 from test_kernels_gpu import ACC_TOL, OUT_TOL   # the 16-bit GEMV's error model: the products a * q are exact
 
 torch.set_grad_enabled(False)
@@ -199,54 +199,33 @@ def test_gemv_w8_kernels_emulated(dtype, N, K):
 
 
 # ---- model ----------------------------------------------------------------------------------------------------------------------
-def _small(lora=False):
-    from stllm_amd import synth
-    from stllm_amd.models.st_llm import STLLMForCausalLM, StllmConfig
-    m = STLLMForCausalLM(StllmConfig(**SMALL), device="cpu")
-    synth.fill_module_(m, 0, "")
-    return m
-
-
-def _decode_run(model, emb, S, n_new, before_decode=None):
-    """prefill S positions, then n_new decode steps: the logits of every step"""
-    lm = model.model
-    B = emb.shape[0]
-    c = lm.new_cache(B, S + n_new + 2, "cpu")
-    lm.prefill(emb[:, :S], None, cache=c)
-    if before_decode is not None:
-        before_decode()
-    out = []
-    for t in range(n_new):
-        _, h = lm.decode_step(emb[:, S + t:S + t + 1], c)
-        out.append(model.logits_from(h, B, 1)[:, 0].clone())
-    return out
-
-
 @pytest.fixture(scope="module")
 def small():
-    return _small()
+    return small_llama(SMALL)
 
 
 @pytest.fixture(scope="module")
 def baseline(small):
-    """decode logits of the 16-bit path on the backend WITHOUT the int8 entry point, computed before tests/_cpu_backend_w8.py is imported by any test here"""
+    """decode logits of the 16-bit path before the int8 mode was ever switched on: no quantised entry point is reached"""
     from stllm_amd import runtime
     emb = T("w8.emb", (2, 12, 256), 0.05)
-    with CB0.installed(), runtime.use_dtype("bf16"):
-        return emb, _decode_run(small, emb, 8, 4)
+    with CB.installed(), runtime.use_dtype("bf16"):
+        CB.CALLS_W8.clear(); CB.CALLS_Q4.clear()
+        base16 = decode_run(small, emb, 8, 4)
+        assert CB.CALLS_W8 == [] and CB.CALLS_Q4 == []
+        return emb, base16
 
 
 def test_int8_decode_equals_the_dequantised_model(small, baseline):
-    import _cpu_backend_w8 as CB
     from stllm_amd import pack, runtime
     emb, base16 = baseline
     lm = small.model
     with CB.installed(), runtime.use_dtype("bf16"):
-        CB.CALLS.clear()
+        CB.CALLS_W8.clear(); CB.CALLS_Q4.clear()
         with runtime.use_decode_weights("int8"):
-            got = _decode_run(small, emb, 8, 4)
-        assert len(CB.CALLS) == 4 * 2 * 4 and all(c[1] == 2 for c in CB.CALLS)
-        assert sum(c[4] for c in CB.CALLS) == 4 * 2 * 2, "B = 2 <= FUSE_NORM_ROWS: the qkv and gate/up projections take the fused-norm form"
+            got = decode_run(small, emb, 8, 4)
+        assert len(CB.CALLS_W8) == 4 * 2 * 4 and all(c[1] == 2 for c in CB.CALLS_W8) and CB.CALLS_Q4 == []
+        assert sum(c[4] for c in CB.CALLS_W8) == 4 * 2 * 2, "B = 2 <= FUSE_NORM_ROWS: the qkv and gate/up projections take the fused-norm form"
         assert runtime.decode_weights() is None
 
         def dequantise():   # the SAME 16-bit decode path over q * scale (fp32 tensors in place of the packed weights; the prefill before it used the originals)
@@ -254,14 +233,14 @@ def test_int8_decode_equals_the_dequantised_model(small, baseline):
                 for k in W8_KEYS:
                     q, s = pack.quant8_rows(pk[k])
                     pk[k] = q.float() * s[:, None]
-        CB.CALLS.clear()
+        CB.CALLS_W8.clear()
         try:
-            want = _decode_run(small, emb, 8, 4, before_decode=dequantise)
+            want = decode_run(small, emb, 8, 4, before_decode=dequantise)
         finally:
             lm.repack()
-        assert CB.CALLS == []
-        # mode None (the default): bit-identical to the run made on the backend without gemv_w8, before the mode was ever switched on
-        again = _decode_run(small, emb, 8, 4)
+        assert CB.CALLS_W8 == []
+        # mode None (the default): bit-identical to the run made before the mode was ever switched on
+        again = decode_run(small, emb, 8, 4)
     scale = max(float(w.abs().max()) for w in want)
     for g, w in zip(got, want):
         assert float((g - w).abs().max()) <= TOL * scale, (float((g - w).abs().max()), scale)
@@ -273,7 +252,6 @@ def test_int8_weight_cache_follows_the_parameters_and_the_mode(small):
     """the int8 copy is keyed by the parameter fingerprint of the 16-bit pack (models/layers.py: `_version` + `data_ptr()`): an in-place edit of a master
     rebuilds both.  (The edit is `p.copy_` as in test_packed_weight_caches_follow_in_place_edits_of_the_masters: a write through `p.data` bypasses
     torch's version counter, for this cache as for the 16-bit one — such writers call repack().)"""
-    import _cpu_backend_w8 as CB
     from stllm_amd import runtime
     lm = small.model
     emb = T("w8.emb", (1, 6, 256), 0.05)
@@ -283,20 +261,20 @@ def test_int8_weight_cache_follows_the_parameters_and_the_mode(small):
         with CB.installed(), runtime.use_dtype("bf16"):
             runtime.set_decode_weights("int8")
             assert runtime.decode_weights() == "int8"
-            a = _decode_run(small, emb, 4, 2)
+            a = decode_run(small, emb, 4, 2)
             assert lm._quant[:2] == ("int8", torch.bfloat16)
             first = lm._quant.layers
             assert set(first[0]) == set(W8_KEYS) and first[1]["wdown"][0].dtype == torch.int8 and first[1]["wdown"][1].shape == (256,)
-            _decode_run(small, emb, 4, 1)
+            decode_run(small, emb, 4, 1)
             assert lm._quant[:2] == ("int8", torch.bfloat16) and lm._quant.layers is first, "unchanged parameters: the cached copy"
             w.copy_(w0 * 1.5)
-            b = _decode_run(small, emb, 4, 2)
+            b = decode_run(small, emb, 4, 2)
             assert lm._quant[:2] == ("int8", torch.bfloat16)
             second = lm._quant.layers
             assert second is not first and not torch.equal(second[1]["wdown"][1], first[1]["wdown"][1])
             assert torch.equal(second[0]["wqkv"][0], first[0]["wqkv"][0]) and not torch.equal(a[-1], b[-1])
             runtime.set_decode_weights(None)
-            _decode_run(small, emb, 4, 1)
+            decode_run(small, emb, 4, 1)
             assert lm._quant is None, "mode off: the int8 copy is freed"
             with pytest.raises(ValueError):
                 runtime.set_decode_weights("int4")
@@ -307,9 +285,8 @@ def test_int8_weight_cache_follows_the_parameters_and_the_mode(small):
 
 
 def test_int8_rejects_the_modes_it_does_not_serve():
-    import _cpu_backend_w8 as CB
     from stllm_amd import runtime
-    m = _small()
+    m = small_llama(SMALL)
     emb = T("w8.emb", (1, 6, 256), 0.05)
     with CB.installed(), runtime.use_decode_weights("int8"):
         with runtime.use_dtype("fp32"):
@@ -324,15 +301,14 @@ def test_int8_rejects_the_modes_it_does_not_serve():
             mod.B.copy_(T(f"w8.lora.B{i}", tuple(mod.B.shape), 0.02))
         with runtime.use_dtype("bf16"):
             with pytest.raises(NotImplementedError, match=r"merge_adapter\(\) first"):
-                _decode_run(m, emb, 4, 1)
+                decode_run(m, emb, 4, 1)
             m.merge_adapter()
-            CB.CALLS.clear()
-            _decode_run(m, emb, 4, 1)
-            assert len(CB.CALLS) == 8
+            CB.CALLS_W8.clear()
+            decode_run(m, emb, 4, 1)
+            assert len(CB.CALLS_W8) == 8
 
 
 def test_generate_runs_through_the_int8_path(small):
-    import _cpu_backend_w8 as CB
     from stllm_amd import runtime
     emb = T("w8.gen", (1, 9, 256), 0.05)
     kw = dict(max_new_tokens=5, do_sample=False, min_length=5)
@@ -342,18 +318,18 @@ def test_generate_runs_through_the_int8_path(small):
         small.model.prefill(emb[:, :5], None, cache=prefix)
         before = [b.clone() for b in prefix.qkv]
         with runtime.use_decode_weights("int8"):
-            CB.CALLS.clear()
+            CB.CALLS_W8.clear()
             ids = small.generate(inputs_embeds=emb[:, 5:], prefix_cache=prefix, num_beams=1, **kw)
-            n1 = len(CB.CALLS)
+            n1 = len(CB.CALLS_W8)
             assert ids.shape == (1, 5) and int(ids.min()) >= 0 and int(ids.max()) < 512
-            assert n1 > 0 and n1 % 8 == 0 and all(c[1] == 1 and c[2:4] in ((768, 256), (256, 256), (1408, 256), (256, 704)) for c in CB.CALLS)
+            assert n1 > 0 and n1 % 8 == 0 and all(c[1] == 1 and c[2:4] in ((768, 256), (256, 256), (1408, 256), (256, 704)) for c in CB.CALLS_W8)
             assert prefix.len == 5 and all(torch.equal(x, y) for x, y in zip(prefix.qkv, before))
-            CB.CALLS.clear()
+            CB.CALLS_W8.clear()
             ids5 = small.generate(inputs_embeds=emb, num_beams=5, **kw)
             assert ids5.shape[0] == 1 and int(ids5.min()) >= 0 and int(ids5.max()) < 512
-            assert len(CB.CALLS) > 0 and len(CB.CALLS) % 8 == 0 and all(c[1] == 5 and not c[4] for c in CB.CALLS), "5 beams: 5 rows, norms not fused"
-        CB.CALLS.clear()
-        assert torch.equal(small.generate(inputs_embeds=emb, num_beams=5, **kw), off) and CB.CALLS == []
+            assert len(CB.CALLS_W8) > 0 and len(CB.CALLS_W8) % 8 == 0 and all(c[1] == 5 and not c[4] for c in CB.CALLS_W8), "5 beams: 5 rows, norms not fused"
+        CB.CALLS_W8.clear()
+        assert torch.equal(small.generate(inputs_embeds=emb, num_beams=5, **kw), off) and CB.CALLS_W8 == []
 
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------------------
