@@ -636,7 +636,16 @@ int stllm_rope_bwd(int dtype, void* d, int64_t ld, const float* cos_t, const flo
  * stllm_attention for all eight operands; masks as in the forward (causal needs Sq == Skv).  D % 8 == 0, D <= 128.
  * bf16 / f16 run on MFMA kernels (the Llama prefill, the Q-Former's 64-wide self- and cross-attention heads, EVA's 88-wide heads padded
  * to 96 in LDS), fp32 on fp32-FMA kernels (also for 16-bit operands with STLLM_ATTN_BWD_VALU=1 in the environment).
- * workspace: stllm_attention_bwd_workspace_bytes(B, H, Sq) (log-sum-exp and dO.o per query row). */
+ * workspace: stllm_attention_bwd_workspace_bytes(B, H, Sq) (log-sum-exp and dO.o per query row), no initialisation needed: every word the second
+ * launch reads was written by the first launch of the same call.
+ * Memory regions.  Never read: q / o / dO rows >= Sq and K / V rows >= Skv of a batch entry (a tile overhanging the end is filled with zeros in the
+ * LDS / registers, not loaded), columns behind H * D of any operand, and dq / dk / dv themselves (outputs only: the caller may pass uninitialised
+ * memory).  READ, WEIGHTLESS, MUST BE FINITE: the K / V rows in [kv_len[b], Skv) — the kernels load whole key tiles up to Skv and zero the
+ * PROBABILITY, and dP = dO V^T of such a row is multiplied by that exact 0: a NaN or Inf there would reach dq, dk and dv.  Query rows at or behind
+ * kv_len[b] are ordinary rows (read; they attend the valid keys).  Written: EVERY element of dq inside [B, Sq, H * D] and of dk and dv inside
+ * [B, Skv, H * D] — also the rows nobody attends: dk and dv rows at or behind kv_len[b] are written as exact 0, so a GEMM may read the whole
+ * block afterwards.  kv_len[b] <= 0: no key is visible, dq, dk and dv of that batch row are written as 0 (zeros, never NaN, as in the decode
+ * kernels).  Never written: columns behind H * D of a row, rows >= Sq (dq) / >= Skv (dk, dv) of a batch entry. */
 int64_t stllm_attention_bwd_workspace_bytes(int B, int H, int Sq);
 int stllm_attention_bwd(int dtype, const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
                         const void* v, int64_t v_bs, int64_t v_rs, const void* o, int64_t o_bs, int64_t o_rs,
