@@ -589,6 +589,72 @@ int stllm_cross_entropy_rows(const float* logits, int64_t ldl, const int32_t* la
  * boundary of blip2.py:36-44, when a GEMM consumes rows of the fp32 stream without a norm in between. */
 int stllm_cast_rows(int dtype, const float* x, int64_t ldx, void* out, int64_t ldo, int M, int D, void* stream);
 
+/*
+ * Token selection on the device (generation.py, selection="device"): what HF's logits processors, warpers and `argmax` / `multinomial` / `topk`
+ * do to one row of next-token logits, in ONE launch with one workgroup per row.  The row is staged once into the LDS as fp32 (columns >= V of the
+ * padded row are never read) and every later pass reads the LDS only; all reductions run in a fixed order, so a launch is bit-reproducible.
+ * V * 4 bytes (+ n_prev * 4 when a penalty applies) must fit the 160 KiB of LDS less 4 KiB of scratch: otherwise STLLM_ERR_UNSUPPORTED, nothing
+ * else runs in its place.  Rows that are all -inf or hold a NaN are outside the contract.
+ *
+ * Per row r, s = logits[r, :V]:
+ *   1. penalty != 1: for every DISTINCT id in prev[r, :n_prev] (ids outside [0, V) are ignored): s[id] = s[id] < 0 ? s[id] * penalty : s[id] / penalty,
+ *      once per id, from the original score (IEEE fp32 multiply / divide)                              — RepetitionPenaltyLogitsProcessor
+ *   2. suppress_eos (cur_len < min_length) and 0 <= eos_id < V: s[eos_id] = -inf                      — MinLengthLogitsProcessor
+ *   3. sample == 0: token = lowest index of max(s).
+ *      sample != 0: s /= temperature; e_i = exp(s_i - max); token i is KEPT iff sum_{j: e_j <= e_i} e_j > (1 - top_p) * sum_j e_j, or i is the argmax
+ *      (TopPLogitsWarper, min_tokens_to_keep = 1; a tie group at the threshold is kept whole; top_p >= 1 keeps every e_i > 0); with Z_kept the sum
+ *      over the kept ids, token = the smallest kept id whose inclusive prefix sum over the kept ids, in id order, exceeds u[r] * Z_kept
+ *      (u[r] in [0, 1), a device float the caller draws); the last kept id if rounding runs past the end.
+ *   4. unfinished (nullable, int32 [rows], in / out): a row at 0 emits pad_id and nothing else; a row that emits eos_id is set to 0.
+ *   5. out[r * out_stride] = token (int32).  aux (nullable, float [rows, 4]): max, log sum exp(s - max), the threshold e-value (0 when greedy),
+ *      Z_kept / Z_all (1 when greedy); rows finished on entry leave their aux untouched.
+ */
+typedef struct stllm_select_args {
+  const float* logits;       /* [rows, ldl] fp32 */
+  int64_t ldl;               /* row stride in floats (>= V; any alignment) */
+  int rows, V;
+  const int32_t* prev;       /* [rows, ld_prev] int32 ids generated so far; may be NULL when n_prev == 0 */
+  int64_t ld_prev;
+  int n_prev;
+  float penalty;             /* 1: none */
+  int suppress_eos;
+  int eos_id;                /* < 0: none */
+  int pad_id;
+  int sample;                /* 0 greedy, 1 top-p sampling */
+  float temperature;         /* > 0 */
+  float top_p;
+  const float* u;            /* [rows], sample only */
+  int32_t* unfinished;       /* nullable */
+  int32_t* out;
+  int64_t out_stride;        /* in elements */
+  float* aux;                /* nullable, [rows, 4] */
+} stllm_select_args;
+int stllm_select_tokens(const stllm_select_args* args, void* stream);
+
+/*
+ * Beam-search candidates: per row r (= prompt * num_beams + beam), lp = s - max - log sum exp(s - max) (log_softmax), then steps 1 and 2 above applied
+ * TO lp (HF's order in beam search), score = lp + beam_score[r]; the k best (1 <= k <= 32, k <= V) ordered by (score descending, token ascending):
+ * cand_score fp32 [rows, k], cand_token int32 [rows, k].  The host merges the num_beams * k candidates of a prompt by (score descending,
+ * beam * V + token ascending): the first 2 * num_beams of that union are what a top-k over num_beams * V scores returns.  Same staging, LDS limit
+ * and error behaviour as stllm_select_tokens.
+ */
+typedef struct stllm_beam_args {
+  const float* logits;
+  int64_t ldl;
+  int rows, V;
+  const int32_t* prev;
+  int64_t ld_prev;
+  int n_prev;
+  float penalty;
+  int suppress_eos;
+  int eos_id;
+  const float* beam_score;   /* [rows] */
+  int k;
+  float* cand_score;         /* [rows, k] */
+  int32_t* cand_token;       /* [rows, k] */
+} stllm_beam_args;
+int stllm_beam_candidates(const stllm_beam_args* args, void* stream);
+
 /* =========================================================================================================================
  * Backward / optimizer entry points.  The reference has no such code of its own: the gradients come
  * from torch.autograd over st_llm.py:116-146 (shifted CE + loss_mvm) driven by HF Trainer + DeepSpeed (train_hf.py,

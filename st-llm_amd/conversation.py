@@ -96,7 +96,8 @@ class Chat:
         video's K / V rows are reused and only [BOS] + question is run (same ids; see prefill_video for the text-conditioned case).  This entry point is the
         `get_context_emb_sim` path (no conv.instruction: video tokens + question), for which the reference OVERRIDES
         repetition_penalty with 1.5 (conversation.py:219-220) whatever the caller passed; instruction=True keeps the argument.
-        share_prefix: the beams read one copy of the prompt's (or the video prefix's) K / V rows (generate(share_prefix=True))."""
+        share_prefix: the beams read one copy of the prompt's (or the video prefix's) K / V rows (generate(share_prefix=True)).
+        **kw reaches generate(): selection="device" (and sync_every=K) selects the tokens with the project's own kernels (generation.generate)."""
         embs, att = self.get_context_emb_ids(img_list, question_ids)
         if not instruction:
             repetition_penalty = 1.5
@@ -127,7 +128,7 @@ class Chat:
         override per question, Chat's stop tokens as per-row stop_sequences (a row that ends in '###' is finished, the others go on).  prefix: a
         prefill_video(img_list) result — the video is prefilled once, forked to the N rows, and only [BOS] + question runs per row.  Returns one
         (text, ids) pair per question, each what answer() returns for that question alone.  share_prefix: the N rows (and their beams) read the prefilled video
-        where it is instead of a fork each (generate(share_prefix=True))."""
+        where it is instead of a fork each (generate(share_prefix=True)).  **kw reaches generate(): selection="device", sync_every=K as in answer()."""
         pairs = [self.get_context_emb_ids(img_list, q) for q in questions_ids]
         if not instruction:
             repetition_penalty = 1.5

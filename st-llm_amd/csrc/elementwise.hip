@@ -1,5 +1,6 @@
 // HBM-bound glue kernels: row gather (token-block assembly / masking / embedding lookup),
 // temporal mean, ViT CLS rows, MVM cosine loss rows.  All fp32, float4-vectorised, coalesced.
+// Below them: token selection on a logits row held in the LDS (stllm_select_tokens, stllm_beam_candidates).
 #include "common.h"
 
 namespace {
@@ -125,7 +126,285 @@ __global__ __launch_bounds__(256) void kv_append_rows_kernel(const char* __restr
   reinterpret_cast<uint4*>(cache + (int64_t)b * batch_stride + (int64_t)ps * row_stride + col0_bytes)[c] = v;
 }
 
+// ---- token selection: stllm_select_tokens / stllm_beam_candidates (include/stllm_hip.h) --------------------------------------------------------------
+// One workgroup per row; the row lives in the LDS as fp32 from the staging on (V <= ~40 k floats), every later pass reads the LDS.  Reductions: a
+// per-thread partial in index order, the xor butterfly inside a wave, the four wave results combined in a fixed order — no atomics, so a launch is
+// bit-reproducible.  The four-entry exchange buffers are double-buffered by `ph`: one barrier per reduction.
+constexpr int kSelThreads = 256;
+constexpr int kSelLdsBytes = 160 * 1024 - 4096;   // dynamic LDS a row may take: the CU's 160 KiB less the static scratch below
+constexpr float kSelNoIndex = 3.0e38f;            // "no candidate yet" index (indices travel as floats: V < 2^24)
+
+struct SelRed { float v[2][4]; float i[2][4]; };
+
+__device__ __forceinline__ float sel_block_sum(float v, SelRed* red, int& ph) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red->v[ph][threadIdx.x >> 6] = v;
+  __syncthreads();
+  const float r = (red->v[ph][0] + red->v[ph][1]) + (red->v[ph][2] + red->v[ph][3]);
+  ph ^= 1;
+  return r;
+}
+
+// (value, index) of the best entry of the block under (value descending, index ascending); every thread receives it
+__device__ __forceinline__ void sel_block_best(float& v, float& i, SelRed* red, int& ph) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64), oi = __shfl_xor(i, o, 64);
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
+  if ((threadIdx.x & 63) == 0) { red->v[ph][threadIdx.x >> 6] = v; red->i[ph][threadIdx.x >> 6] = i; }
+  __syncthreads();
+  v = red->v[ph][0]; i = red->i[ph][0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const float ov = red->v[ph][w], oi = red->i[ph][w];
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
+  ph ^= 1;
+}
+
+// repetition penalty on the staged row: every id's new value is computed from the ORIGINAL score into pv[j] before any score is rewritten, so a
+// repeated id writes the same value again (once per distinct id).  Ids outside [0, V) are skipped.  Ends with the row visible to every thread.
+__device__ __forceinline__ void sel_penalise(float* s, float* pv, const int32_t* prev, int n_prev, int V, float pen) {
+  for (int j = threadIdx.x; j < n_prev; j += kSelThreads) {
+    const int id = prev[j];
+    if ((unsigned)id < (unsigned)V) { const float x = s[id]; pv[j] = x < 0.0f ? x * pen : __fdiv_rn(x, pen); }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < n_prev; j += kSelThreads) {
+    const int id = prev[j];
+    if ((unsigned)id < (unsigned)V) s[id] = pv[j];
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kSelThreads) void select_tokens_kernel(const stllm_select_args a) {
+  extern __shared__ float smem[];                 // [V] scores, then [n_prev] penalised values
+  __shared__ SelRed red;
+  __shared__ float csum[kSelThreads];             // per-chunk kept sums, then their inclusive prefix
+  __shared__ int clast[kSelThreads];              // last kept id of a chunk, -1: none
+  __shared__ float gbase[kSelThreads / 16];
+  const int row = blockIdx.x, tid = threadIdx.x, V = a.V;
+  int32_t* out = a.out + (int64_t)row * a.out_stride;
+  if (a.unfinished && a.unfinished[row] == 0) {   // a finished row emits pad (uniform over the block)
+    if (tid == 0) *out = a.pad_id;
+    return;
+  }
+  float* s = smem;
+  const float* x = a.logits + (int64_t)row * a.ldl;
+  for (int c = tid; c < V; c += kSelThreads) s[c] = x[c];
+  __syncthreads();
+  if (a.penalty != 1.0f && a.n_prev > 0) sel_penalise(s, s + V, a.prev + (int64_t)row * a.ld_prev, a.n_prev, V, a.penalty);
+  if (a.suppress_eos && tid == 0 && (unsigned)a.eos_id < (unsigned)V) s[a.eos_id] = -INFINITY;
+  __syncthreads();
+  // from here to the chunked walk a thread touches only the columns c = tid (mod 256): no barrier is needed between those passes
+  const bool sample = a.sample != 0;
+  const bool warm = sample && a.temperature != 1.0f;
+  int ph = 0;
+  float bv = -INFINITY, bi = kSelNoIndex;
+  for (int c = tid; c < V; c += kSelThreads) {
+    float v = s[c];
+    if (warm) { v = __fdiv_rn(v, a.temperature); s[c] = v; }
+    if (v > bv) { bv = v; bi = (float)c; }
+  }
+  sel_block_best(bv, bi, &red, ph);
+  const float mx = bv;
+  const int amax = bi < (float)V ? (int)bi : 0;
+  if (!sample) {
+    if (a.aux) {
+      float z = 0.0f;
+      for (int c = tid; c < V; c += kSelThreads) z += expf(s[c] - mx);
+      z = sel_block_sum(z, &red, ph);
+      if (tid == 0) { float* ax = a.aux + (int64_t)row * 4; ax[0] = mx; ax[1] = logf(z); ax[2] = 0.0f; ax[3] = 1.0f; }
+    }
+    if (tid == 0) {
+      *out = amax;
+      if (a.unfinished && amax == a.eos_id) a.unfinished[row] = 0;
+    }
+    return;
+  }
+  float z = 0.0f;
+  for (int c = tid; c < V; c += kSelThreads) { const float e = expf(s[c] - mx); s[c] = e; z += e; }
+  const float Z = sel_block_sum(z, &red, ph);
+  // threshold = the smallest e-value t with sum_{e_j <= t} e_j > (1 - top_p) Z, found by bisection on the bit pattern (monotone for floats >= 0; the
+  // masked sum runs in the same order every pass, so it is monotone in the mask).  exp(0) = 1 is the largest value there is.
+  const uint32_t one = 0x3f800000u;
+  uint32_t tb;
+  if (a.top_p >= 1.0f) {
+    tb = 1u;                                      // every e > 0
+  } else {
+    const float thr = (1.0f - a.top_p) * Z;
+    if (!(Z > thr)) {
+      tb = one + 1u;                              // nothing passes: the argmax alone (min_tokens_to_keep)
+    } else {
+      uint32_t lo = 0u, hi = one;
+      while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        float p = 0.0f;
+#pragma unroll 8
+        for (int c = tid; c < V; c += kSelThreads) { const float e = s[c]; p += __builtin_bit_cast(uint32_t, e) <= mid ? e : 0.0f; }   // (8 LDS reads in flight; the adds keep their order)
+        p = sel_block_sum(p, &red, ph);
+        if (p > thr) hi = mid; else lo = mid + 1u;
+      }
+      tb = lo;
+    }
+  }
+  __syncthreads();                                // the walk owns contiguous chunks: other threads' e-values
+  const int chunk = (V + kSelThreads - 1) / kSelThreads;
+  const int c0 = min(V, tid * chunk), c1 = min(V, c0 + chunk);
+  float cs = 0.0f;
+  int last = -1;
+  for (int c = c0; c < c1; ++c) {
+    const float e = s[c];
+    if (__builtin_bit_cast(uint32_t, e) >= tb || c == amax) { cs += e; last = c; }
+  }
+  csum[tid] = cs; clast[tid] = last;
+  __syncthreads();
+  if (tid != 0) return;
+  // inclusive prefix of the chunk sums on two levels (16 x 16): no chain is longer than 32 adds
+  float G = 0.0f;
+  int lastk = amax;
+  for (int g = 0; g < kSelThreads; g += 16) {
+    float gs = 0.0f, run = G;
+    gbase[g >> 4] = G;
+    for (int t = g; t < g + 16; ++t) {
+      const float c = csum[t];
+      gs += c; run += c; csum[t] = run;
+      if (clast[t] >= 0) lastk = clast[t];
+    }
+    G += gs;
+  }
+  const float Zk = G, target = a.u[row] * Zk;
+  int tok = lastk;                                // rounding ran past the end: the last kept id
+  for (int t = 0; t < kSelThreads; ++t) {
+    if (clast[t] < 0 || !(csum[t] > target)) continue;
+    float run = (t & 15) ? csum[t - 1] : gbase[t >> 4];
+    tok = clast[t];
+    const int d0 = min(V, t * chunk), d1 = min(V, d0 + chunk);
+    for (int c = d0; c < d1; ++c) {
+      const float e = s[c];
+      if (__builtin_bit_cast(uint32_t, e) >= tb || c == amax) {
+        run += e;
+        if (run > target) { tok = c; break; }
+      }
+    }
+    break;
+  }
+  *out = tok;
+  if (a.unfinished && tok == a.eos_id) a.unfinished[row] = 0;
+  if (a.aux) {
+    float* ax = a.aux + (int64_t)row * 4;
+    ax[0] = mx; ax[1] = logf(Z); ax[2] = __builtin_bit_cast(float, tb); ax[3] = __fdiv_rn(Zk, Z);
+  }
+}
+
+__global__ __launch_bounds__(kSelThreads) void beam_candidates_kernel(const stllm_beam_args a) {
+  extern __shared__ float smem[];                 // [V] scores, then [n_prev] penalised values
+  __shared__ SelRed red;
+  const int row = blockIdx.x, tid = threadIdx.x, V = a.V;
+  float* s = smem;
+  const float* x = a.logits + (int64_t)row * a.ldl;
+  int ph = 0;
+  float bv = -INFINITY, bi = kSelNoIndex;
+  for (int c = tid; c < V; c += kSelThreads) {
+    const float v = x[c];
+    s[c] = v;
+    if (v > bv) { bv = v; bi = (float)c; }
+  }
+  sel_block_best(bv, bi, &red, ph);
+  const float mx = bv;
+  float z = 0.0f;
+  for (int c = tid; c < V; c += kSelThreads) z += expf(s[c] - mx);
+  const float lse = logf(sel_block_sum(z, &red, ph));
+  for (int c = tid; c < V; c += kSelThreads) s[c] = (s[c] - mx) - lse;   // log_softmax
+  __syncthreads();
+  if (a.penalty != 1.0f && a.n_prev > 0) sel_penalise(s, s + V, a.prev + (int64_t)row * a.ld_prev, a.n_prev, V, a.penalty);
+  if (a.suppress_eos && tid == 0 && (unsigned)a.eos_id < (unsigned)V) s[a.eos_id] = -INFINITY;
+  __syncthreads();
+  const float bs = a.beam_score[row];
+  for (int c = tid; c < V; c += kSelThreads) s[c] += bs;
+  // k rounds of "the best entry strictly behind the previous pick" in the order (score descending, token ascending): nothing is rewritten, so
+  // tied scores (-inf, or everything behind a -1e9 beam score) come out once each, in token order
+  float lv = INFINITY, li = -1.0f;
+  for (int r = 0; r < a.k; ++r) {
+    bv = -INFINITY; bi = kSelNoIndex;
+#pragma unroll 8
+    for (int c = tid; c < V; c += kSelThreads) {
+      const float v = s[c], fc = (float)c;
+      if ((v < lv || (v == lv && fc > li)) && (v > bv || bi == kSelNoIndex)) { bv = v; bi = fc; }
+    }
+    sel_block_best(bv, bi, &red, ph);
+    if (tid == 0) {
+      a.cand_score[(int64_t)row * a.k + r] = bv;
+      a.cand_token[(int64_t)row * a.k + r] = bi < (float)V ? (int)bi : 0;
+    }
+    lv = bv; li = bi;
+  }
+}
+
+// dynamic LDS of a selection launch, or -1 when the row does not fit
+int sel_lds_bytes(int V, int n_prev, float penalty) {
+  const int64_t need = ((int64_t)V + (penalty != 1.0f ? n_prev : 0)) * 4;
+  return need > kSelLdsBytes ? -1 : (int)((need + 15) & ~(int64_t)15);
+}
+
 }  // namespace
+
+extern "C" int stllm_select_tokens(const stllm_select_args* a, void* stream) {
+  STLLM_CHECK_ARG(a != nullptr, "stllm_select_tokens: null args");
+  STLLM_CHECK_ARG(a->logits && a->out && a->rows > 0 && a->V > 0 && a->ldl >= a->V, "stllm_select_tokens: bad logits / out / rows=%d V=%d ldl=%lld", a->rows,
+                  a->V, (long long)a->ldl);
+  STLLM_CHECK_ARG(a->n_prev >= 0 && (a->n_prev == 0 || (a->prev && a->ld_prev >= a->n_prev)), "stllm_select_tokens: prev needs n_prev <= ld_prev");
+  STLLM_CHECK_ARG(a->penalty > 0.0f, "stllm_select_tokens: penalty must be positive");
+  STLLM_CHECK_ARG(!a->sample || (a->u && a->temperature > 0.0f && a->top_p > 0.0f), "stllm_select_tokens(sample): needs u, temperature > 0, top_p > 0");
+  const int lds = sel_lds_bytes(a->V, a->n_prev, a->penalty);
+  if (lds < 0) {
+    stllm_set_error("stllm_select_tokens: V=%d (+ n_prev=%d) floats do not fit %d bytes of LDS", a->V, a->n_prev, kSelLdsBytes);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  static StllmPerDevice lds_dev;   // largest dynamic-LDS size opted into, per device ordinal
+  bool lds_first;
+  const int lds_d = lds_dev.enter(&lds_first);
+  if (lds_first || lds > lds_dev.value[lds_d]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(select_tokens_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+      stllm_set_error("stllm_select_tokens: cannot opt into %d bytes of LDS", lds);
+      return STLLM_ERR_UNSUPPORTED;
+    }
+    lds_dev.value[lds_d] = lds;
+    lds_dev.done(lds_d);
+  }
+  hipLaunchKernelGGL(select_tokens_kernel, dim3(a->rows), dim3(kSelThreads), lds, reinterpret_cast<hipStream_t>(stream), *a);
+  STLLM_CHECK_LAUNCH("stllm_select_tokens");
+  return STLLM_OK;
+}
+
+extern "C" int stllm_beam_candidates(const stllm_beam_args* a, void* stream) {
+  STLLM_CHECK_ARG(a != nullptr, "stllm_beam_candidates: null args");
+  STLLM_CHECK_ARG(a->logits && a->beam_score && a->cand_score && a->cand_token && a->rows > 0 && a->V > 0 && a->ldl >= a->V,
+                  "stllm_beam_candidates: bad pointers / rows=%d V=%d ldl=%lld", a->rows, a->V, (long long)a->ldl);
+  STLLM_CHECK_ARG(a->k >= 1 && a->k <= 32 && a->k <= a->V, "stllm_beam_candidates: 1 <= k=%d <= min(32, V=%d)", a->k, a->V);
+  STLLM_CHECK_ARG(a->n_prev >= 0 && (a->n_prev == 0 || (a->prev && a->ld_prev >= a->n_prev)), "stllm_beam_candidates: prev needs n_prev <= ld_prev");
+  STLLM_CHECK_ARG(a->penalty > 0.0f, "stllm_beam_candidates: penalty must be positive");
+  const int lds = sel_lds_bytes(a->V, a->n_prev, a->penalty);
+  if (lds < 0) {
+    stllm_set_error("stllm_beam_candidates: V=%d (+ n_prev=%d) floats do not fit %d bytes of LDS", a->V, a->n_prev, kSelLdsBytes);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  static StllmPerDevice lds_dev;   // largest dynamic-LDS size opted into, per device ordinal
+  bool lds_first;
+  const int lds_d = lds_dev.enter(&lds_first);
+  if (lds_first || lds > lds_dev.value[lds_d]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(beam_candidates_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+      stllm_set_error("stllm_beam_candidates: cannot opt into %d bytes of LDS", lds);
+      return STLLM_ERR_UNSUPPORTED;
+    }
+    lds_dev.value[lds_d] = lds;
+    lds_dev.done(lds_d);
+  }
+  hipLaunchKernelGGL(beam_candidates_kernel, dim3(a->rows), dim3(kSelThreads), lds, reinterpret_cast<hipStream_t>(stream), *a);
+  STLLM_CHECK_LAUNCH("stllm_beam_candidates");
+  return STLLM_OK;
+}
 
 extern "C" int stllm_kv_append_rows(int dtype, const void* src, int64_t ld_src, void* cache, int64_t batch_stride, int64_t row_stride,
                                     const int32_t* pos, int B, int hidden, int max_len, int with_q, void* stream) {

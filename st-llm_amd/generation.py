@@ -163,9 +163,14 @@ class _CacheStepper:
             self.emb = emb.repeat_interleave(self.rep, dim=0)
             self.logits = self.m.forward(samples=None, inputs_embeds=self.emb).logits[:, -1].float()
 
-    def advance(self, next_tokens, beam_idx=None):
-        """append `next_tokens` [rows] (after re-ordering the rows by `beam_idx`) and compute the next logits"""
-        tok = self.lm.embed_tokens(next_tokens.view(-1, 1).cpu())
+    def advance(self, next_tokens, beam_idx=None, on_device=False):
+        """append `next_tokens` [rows] (after re-ordering the rows by `beam_idx`) and compute the next logits.
+        on_device: `next_tokens` is a contiguous int32 tensor on the device and stays there — the embedding rows are gathered by it directly"""
+        if on_device:
+            from . import hip
+            tok = hip.gather_rows(self.lm.embed_tokens.weight, next_tokens).view(next_tokens.numel(), 1, -1)
+        else:
+            tok = self.lm.embed_tokens(next_tokens.view(-1, 1).cpu())
         if self.use_cache:
             if beam_idx is not None and not torch.equal(beam_idx.cpu(), torch.arange(beam_idx.numel())):
                 n = self.cache.len - self.cache.base_len   # a shared base is common to the beams of a prompt: only the positions behind it move
@@ -187,7 +192,7 @@ class _CacheStepper:
 def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sample=False, min_length=0, top_p=1.0,
              temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, stopping_criteria=None, eos_token_id=2,
              pad_token_id=0, use_cache=True, generator=None, prefix=None, lengths=None, stop_sequences=None, return_lengths=False,
-             share_prefix=False):
+             share_prefix=False, selection="torch", sync_every=1):
     """Returns the generated ids [B, n] (the prompt has no ids), HF semantics as described in the module docstring.
     prefix: a KVCache that already holds the first positions of every prompt (LlamaModel.prefill(cache=...) / Chat.prefill_video); `inputs_embeds` is then
     the remainder of the prompt, appended behind it in one pass (LlamaModel.extend).  The prefix is left unchanged.
@@ -197,10 +202,25 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
     return_lengths: also return the number of generated tokens per row (the rest of the row is padding).
     share_prefix: the rows that have the same first positions — the questions behind one prefix row, the beams of a prompt — read ONE physical copy of them
     (KVCache.share, hip.attention_shared) instead of owning a copy each; the beam re-ordering then moves the positions behind it only.
-    Same ids up to the summation order of the attention; needs use_cache.  False (default): every row owns its copy, as always."""
+    Same ids up to the summation order of the attention; needs use_cache.  False (default): every row owns its copy, as always.
+    selection: "torch" (default) selects every token with torch operators, as always.  "device" (opt-in) selects it with the project's
+    own kernels — hip.select_tokens on the logits where `logits_from` wrote them, into column t of an int32 ids buffer that stays on the device and feeds
+    the next embedding lookup; beam search takes the 2 * num_beams best candidates of every beam from hip.beam_candidates, merges them per prompt on the
+    host and runs the same scorer.  Greedy and beam search give the ids of "torch" (up to fp32 rounding between near-tied scores).  Sampling draws ONE
+    uniform number per row and step (torch.rand(rows, generator=generator)) and inverts the kept distribution's CDF in id order, so for the same seed its
+    ids DIFFER from those of torch.multinomial; the same seed reproduces them.  A vocabulary that does not fit the LDS raises.
+    sync_every: "device", num_beams == 1 only — the host reads `unfinished` back every sync_every-th step instead of every step; finished rows emit
+    pad_token_id meanwhile, and the result is cut where every row had finished: the same ids.  A `stopping_criteria` callable needs the ids of every
+    step and forces 1."""
     B = inputs_embeds.shape[0]
     dev = inputs_embeds.device
     stop_sequences = list(stop_sequences) if stop_sequences else None
+    if selection not in ("torch", "device"):
+        raise ValueError(f"generate(selection={selection!r}): 'torch' or 'device'")
+    on_device = selection == "device"
+    if on_device and num_beams == 1:
+        return _generate_device(lm_wrapper, inputs_embeds, max_new_tokens, do_sample, min_length, top_p, temperature, repetition_penalty, stopping_criteria,
+                                eos_token_id, pad_token_id, use_cache, generator, prefix, lengths, stop_sequences, return_lengths, share_prefix, sync_every)
     if num_beams == 1:
         st = _CacheStepper(lm_wrapper, inputs_embeds, B, max_new_tokens, use_cache, prefix, lengths, share_prefix)
         ids = torch.zeros((B, 0), dtype=torch.long, device=dev)
@@ -239,17 +259,20 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
     done = [False] * B
     while True:
         cur_len = ids.shape[1]
-        logp = st.logits.to(dev).log_softmax(dim=-1)
-        logp = _process_logits(logp, ids, cur_len, repetition_penalty, min_length, eos_token_id)
-        V = logp.shape[-1]
-        cand = (logp + beam_scores[:, None]).view(B, nb * V)
-        cand_scores, cand_tokens = torch.topk(cand, 2 * nb, dim=1, largest=True, sorted=True)
-        cand_beams = torch.div(cand_tokens, V, rounding_mode="floor")
-        cand_tokens = cand_tokens % V
+        if on_device:
+            cs, ct, cb = _device_candidates(st.logits, ids, beam_scores, B, nb, repetition_penalty, cur_len < min_length, eos_token_id)
+        else:
+            logp = st.logits.to(dev).log_softmax(dim=-1)
+            logp = _process_logits(logp, ids, cur_len, repetition_penalty, min_length, eos_token_id)
+            V = logp.shape[-1]
+            cand = (logp + beam_scores[:, None]).view(B, nb * V)
+            cand_scores, cand_tokens = torch.topk(cand, 2 * nb, dim=1, largest=True, sorted=True)
+            cand_beams = torch.div(cand_tokens, V, rounding_mode="floor")
+            cand_tokens = cand_tokens % V
+            cs, ct, cb = cand_scores.cpu(), cand_tokens.cpu(), cand_beams.cpu()
         next_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
         next_tokens = torch.zeros((B, nb), dtype=torch.long, device=dev)
         next_index = torch.zeros((B, nb), dtype=torch.long, device=dev)
-        cs, ct, cb = cand_scores.cpu(), cand_tokens.cpu(), cand_beams.cpu()
         for b in range(B):                                   # BeamSearchScorer.process
             if done[b]:
                 next_scores[b] = 0
@@ -282,7 +305,10 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
                     done[b] = True
         if all(done) or _stop(stopping_criteria, ids, None) or ids.shape[1] >= max_new_tokens:
             break
-        st.advance(next_tokens.view(-1), beam_idx)
+        if on_device:
+            st.advance(next_tokens.view(-1).to(torch.int32), beam_idx, on_device=True)
+        else:
+            st.advance(next_tokens.view(-1), beam_idx)
     # BeamSearchScorer.finalize: open beams become hypotheses, best one wins, EOS appended when it ended early
     out = []
     for b in range(B):
@@ -298,6 +324,66 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
             res[b, len(o)] = eos_token_id
     _check_exchanges(dev)
     return (res, [min(len(o) + 1, sent_max) for o in out]) if return_lengths else res
+
+
+def _device_candidates(logits, ids, beam_scores, B, nb, repetition_penalty, suppress_eos, eos_token_id):
+    """selection="device": what `topk` over the nb * V scores of a prompt returns, from hip.beam_candidates.  Every beam row gives its k = 2 * nb best
+    (score descending, token ascending); ONE device -> host copy brings the nb * k (score, token) pairs of every prompt over, and the host merges them by
+    (score descending, beam * V + token ascending).  Returns CPU tensors (scores f32, tokens, beams) [B, 2 * nb]."""
+    from . import hip
+    rows, k, V = B * nb, 2 * nb, logits.shape[-1]
+    if k > min(32, V):
+        raise ValueError(f"generate(selection='device'): 2 * num_beams = {k} candidates per beam exceed min(32, vocabulary {V})")
+    n_prev = ids.shape[1]
+    buf = torch.empty((2, rows, k), dtype=torch.int32, device=logits.device)   # scores (as fp32 bits) and tokens side by side: one copy back
+    hip.beam_candidates(logits, beam_scores.contiguous(), k, prev=ids.to(torch.int32) if n_prev else None, n_prev=n_prev, penalty=repetition_penalty,
+                        suppress_eos=suppress_eos and eos_token_id is not None, eos_id=eos_token_id, cand_score=buf[0].view(torch.float32), cand_token=buf[1])
+    host = buf.cpu()
+    sc, tk = host[0].view(torch.float32).view(B, nb * k), host[1].view(B, nb * k)
+    beam = torch.arange(nb).repeat_interleave(k)
+    cs, ct, cb = (torch.empty((B, k), dtype=dt) for dt in (torch.float32, torch.long, torch.long))
+    for b in range(B):
+        order = sorted(range(nb * k), key=lambda i: (-float(sc[b, i]), int(beam[i]) * V + int(tk[b, i])))[:k]
+        cs[b], ct[b], cb[b] = sc[b, order], tk[b, order].long(), beam[order]
+    return cs, ct, cb
+
+
+def _generate_device(lm_wrapper, inputs_embeds, max_new_tokens, do_sample, min_length, top_p, temperature, repetition_penalty, stopping_criteria,
+                     eos_token_id, pad_token_id, use_cache, generator, prefix, lengths, stop_sequences, return_lengths, share_prefix, sync_every):
+    """greedy search / sampling of generate(selection="device"): one hip.select_tokens launch per step, the ids stay on the device"""
+    from . import hip
+    B, dev = inputs_embeds.shape[0], inputs_embeds.device
+    st = _CacheStepper(lm_wrapper, inputs_embeds, B, max_new_tokens, use_cache, prefix, lengths, share_prefix)
+    ids = torch.full((B, max_new_tokens), pad_token_id, dtype=torch.int32, device=dev)
+    track = eos_token_id is not None or bool(stop_sequences)     # rows can finish: the kernel keeps `unfinished`
+    unfinished = torch.ones(B, dtype=torch.int32, device=dev)
+    n_gen = torch.zeros(B, dtype=torch.int32, device=dev)
+    every = 1 if stopping_criteria is not None else max(1, int(sync_every))
+    nxt = torch.empty(B, dtype=torch.int32, device=dev)
+    u, t = None, 0
+    while True:
+        n_gen += unfinished
+        if do_sample:
+            u = torch.rand(B, generator=generator, device=generator.device if generator is not None else dev).to(dev)
+        hip.select_tokens(st.logits, ids[:, t], prev=ids, n_prev=t, penalty=repetition_penalty,
+                          suppress_eos=eos_token_id is not None and t < min_length, eos_id=eos_token_id, pad_id=pad_token_id, sample=do_sample,
+                          temperature=temperature, top_p=top_p, u=u, unfinished=unfinished if track else None)
+        t += 1
+        if stop_sequences:
+            unfinished *= (~_ends_in_stop(ids[:, :t], stop_sequences)).to(torch.int32)
+        if t >= max_new_tokens:
+            break
+        if stopping_criteria is not None and _stop(stopping_criteria, ids[:, :t].long(), None):
+            break
+        if track and t % every == 0 and int(unfinished.max()) == 0:
+            break
+        nxt.copy_(ids[:, t - 1])                                 # the gather's index operand is a dense vector: one 4 * B-byte device copy
+        st.advance(nxt, on_device=True)
+    n_host = n_gen.tolist()
+    n = t if stopping_criteria is not None else max(n_host)      # sync_every > 1 runs past the step at which every row had finished: cut there
+    out = ids[:, :n].long()
+    _check_exchanges(dev)
+    return (out, n_host) if return_lengths else out
 
 
 def _check_exchanges(dev):

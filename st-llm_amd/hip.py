@@ -29,7 +29,7 @@ EXPORTS = ["stllm_last_error", "stllm_abi_version", "stllm_last_kernel", "stllm_
            "stllm_lora_down_workspace_bytes", "stllm_lora_down", "stllm_llama_layers_lora_scratch_bytes", "stllm_llama_layers_lora",
            "stllm_attention_offset_workspace_bytes", "stllm_attention_offset", "stllm_llama_layers_extend", "stllm_gemv_w8", "stllm_gemv_q4",
            "stllm_attention_decode_ragged_workspace_bytes", "stllm_attention_decode_ragged", "stllm_kv_append_rows",
-           "stllm_attention_shared_workspace_bytes", "stllm_attention_shared"]
+           "stllm_attention_shared_workspace_bytes", "stllm_attention_shared", "stllm_select_tokens", "stllm_beam_candidates"]
 
 
 def torch_dtype(d):
@@ -70,6 +70,20 @@ class GemvQ4Args(ctypes.Structure):
                 ("rope_cos", c_void_p), ("rope_sin", c_void_p), ("rope_seq", c_int), ("rope_cols", c_int),
                 ("a_rows_per_batch", c_int), ("a_batch_stride", c_int64), ("o_rows_per_batch", c_int), ("o_batch_stride", c_int64),
                 ("a_norm_x", c_void_p), ("a_norm_ldx", c_int64), ("a_norm_gamma", c_void_p), ("a_norm_eps", c_float)]
+
+
+class SelectArgs(ctypes.Structure):
+    """stllm_select_args (include/stllm_hip.h)"""
+    _fields_ = [("logits", c_void_p), ("ldl", c_int64), ("rows", c_int), ("V", c_int), ("prev", c_void_p), ("ld_prev", c_int64), ("n_prev", c_int),
+                ("penalty", c_float), ("suppress_eos", c_int), ("eos_id", c_int), ("pad_id", c_int), ("sample", c_int), ("temperature", c_float),
+                ("top_p", c_float), ("u", c_void_p), ("unfinished", c_void_p), ("out", c_void_p), ("out_stride", c_int64), ("aux", c_void_p)]
+
+
+class BeamArgs(ctypes.Structure):
+    """stllm_beam_args (include/stllm_hip.h)"""
+    _fields_ = [("logits", c_void_p), ("ldl", c_int64), ("rows", c_int), ("V", c_int), ("prev", c_void_p), ("ld_prev", c_int64), ("n_prev", c_int),
+                ("penalty", c_float), ("suppress_eos", c_int), ("eos_id", c_int), ("beam_score", c_void_p), ("k", c_int), ("cand_score", c_void_p),
+                ("cand_token", c_void_p)]
 
 
 class VitBlockWeights(ctypes.Structure):
@@ -193,6 +207,8 @@ def _bind(L, strict=True):
     B("stllm_llama_layers_extend", [ctypes.POINTER(LlamaLayersArgs), ctypes.POINTER(LlamaLayerWeights), c_int, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_gemv_w8", [ctypes.POINTER(GemvW8Args), c_void_p])
     B("stllm_gemv_q4", [ctypes.POINTER(GemvQ4Args), c_void_p])
+    B("stllm_select_tokens", [ctypes.POINTER(SelectArgs), c_void_p])
+    B("stllm_beam_candidates", [ctypes.POINTER(BeamArgs), c_void_p])
     B("stllm_gemm_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     B("stllm_gemm_w4_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     return L
@@ -1080,6 +1096,72 @@ def gather_rows(src_a, idx_a, *, src_b=None, add=None, idx_add=None, out=None, s
                                    _p(idx_a), _p(add), add.stride(0) if add is not None else 0, _p(idx_add),
                                    _p(out), out.stride(0), n, D, scale, _stream()), "stllm_gather_rows")
     return out
+
+
+def _sel_rows(logits, prev, n_prev, what):
+    """common operands of the two selection entry points: fp32 logits rows (any row stride: `logits_from` returns a view of the padded rows) and the
+    int32 ids generated so far, of which the first n_prev columns count"""
+    _req(logits, torch.float32, "logits")
+    if logits.dim() != 2:
+        raise RuntimeError(f"{what}: logits must be [rows, V], got {tuple(logits.shape)}")
+    rows = logits.shape[0]
+    if n_prev:
+        _req(prev, torch.int32, "prev")
+        if prev.dim() != 2 or prev.shape[0] != rows or prev.shape[1] < n_prev:
+            raise RuntimeError(f"{what}: prev {tuple(prev.shape)} does not hold {n_prev} ids for each of {rows} rows")
+    return rows, logits.shape[1], (logits.stride(0) if rows > 1 else max(logits.stride(0), logits.shape[1]))
+
+
+def select_tokens(logits, out, *, prev=None, n_prev=0, penalty=1.0, suppress_eos=False, eos_id=None, pad_id=0, sample=False, temperature=1.0, top_p=1.0,
+                  u=None, unfinished=None, aux=None):
+    """stllm_select_tokens: the next token of every row of `logits` f32 [rows, V] -> out (int32 [rows] view, any element stride: a column of the ids buffer).
+    Repetition penalty over the distinct ids prev[r, :n_prev], EOS suppression, then argmax (lowest index) or temperature / top-p sampling driven by
+    u f32 [rows] in [0, 1).  unfinished int32 [rows] (in / out): rows at 0 emit pad_id, rows that emit eos_id are set to 0.  aux f32 [rows, 4] (optional):
+    max, log-sum-exp - max, threshold e-value, kept mass.  A vocabulary that does not fit the LDS raises (no other path runs)."""
+    rows, V, ldl = _sel_rows(logits, prev, n_prev, "select_tokens")
+    _req(out.unsqueeze(-1), torch.int32, "out")   # device and dtype only: a strided column of the ids buffer is what this output is for
+    if out.dim() != 1 or out.numel() != rows:
+        raise RuntimeError(f"select_tokens: out must be int32 [{rows}], got {tuple(out.shape)}")
+    if sample:
+        _req(u, torch.float32, "u")
+        if u.numel() != rows or not u.is_contiguous():
+            raise RuntimeError("select_tokens(sample): u must be contiguous f32 [rows]")
+    if unfinished is not None:
+        _req(unfinished, torch.int32, "unfinished")
+        if unfinished.numel() != rows or not unfinished.is_contiguous():
+            raise RuntimeError("select_tokens: unfinished must be contiguous int32 [rows]")
+    if aux is not None:
+        _req(aux, torch.float32, "aux")
+        if tuple(aux.shape) != (rows, 4) or not aux.is_contiguous():
+            raise RuntimeError("select_tokens: aux must be contiguous f32 [rows, 4]")
+    a = SelectArgs(logits=logits.data_ptr(), ldl=ldl, rows=rows, V=V, prev=prev.data_ptr() if n_prev else None, ld_prev=prev.stride(0) if n_prev else 0,
+                   n_prev=n_prev, penalty=penalty, suppress_eos=int(bool(suppress_eos)), eos_id=-1 if eos_id is None else int(eos_id), pad_id=int(pad_id),
+                   sample=int(bool(sample)), temperature=temperature, top_p=top_p, u=u.data_ptr() if sample else None,
+                   unfinished=unfinished.data_ptr() if unfinished is not None else None, out=out.data_ptr(), out_stride=out.stride(0) if rows > 1 else 1,
+                   aux=aux.data_ptr() if aux is not None else None)
+    _check(lib().stllm_select_tokens(ctypes.byref(a), _stream()), "stllm_select_tokens")
+    return out
+
+
+def beam_candidates(logits, beam_score, k, *, prev=None, n_prev=0, penalty=1.0, suppress_eos=False, eos_id=None, cand_score=None, cand_token=None):
+    """stllm_beam_candidates: per row the k best of log_softmax(logits) (penalised over prev[r, :n_prev], EOS suppressed) + beam_score[r], ordered by
+    (score descending, token ascending) -> (cand_score f32 [rows, k], cand_token int32 [rows, k]).  1 <= k <= min(32, V)."""
+    rows, V, ldl = _sel_rows(logits, prev, n_prev, "beam_candidates")
+    _req(beam_score, torch.float32, "beam_score")
+    if beam_score.numel() != rows or not beam_score.is_contiguous():
+        raise RuntimeError("beam_candidates: beam_score must be contiguous f32 [rows]")
+    if cand_score is None:
+        cand_score = torch.empty((rows, k), dtype=torch.float32, device=logits.device)
+    if cand_token is None:
+        cand_token = torch.empty((rows, k), dtype=torch.int32, device=logits.device)
+    _req(cand_score, torch.float32, "cand_score"); _req(cand_token, torch.int32, "cand_token")
+    if tuple(cand_score.shape) != (rows, k) or tuple(cand_token.shape) != (rows, k) or not cand_score.is_contiguous() or not cand_token.is_contiguous():
+        raise RuntimeError(f"beam_candidates: cand_score / cand_token must be contiguous [{rows}, {k}]")
+    a = BeamArgs(logits=logits.data_ptr(), ldl=ldl, rows=rows, V=V, prev=prev.data_ptr() if n_prev else None, ld_prev=prev.stride(0) if n_prev else 0,
+                 n_prev=n_prev, penalty=penalty, suppress_eos=int(bool(suppress_eos)), eos_id=-1 if eos_id is None else int(eos_id),
+                 beam_score=beam_score.data_ptr(), k=int(k), cand_score=cand_score.data_ptr(), cand_token=cand_token.data_ptr())
+    _check(lib().stllm_beam_candidates(ctypes.byref(a), _stream()), "stllm_beam_candidates")
+    return cand_score, cand_token
 
 
 def mean_t(x):

@@ -788,7 +788,7 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
     def generate(self, inputs_embeds=None, max_new_tokens=16, num_beams=1, do_sample=False, stopping_criteria=None,
                  attention_mask=None, use_cache=True, min_length=0, top_p=1.0, repetition_penalty=1.0, length_penalty=1.0,
                  temperature=1.0, eos_token_id=2, pad_token_id=0, generator=None, prefix_cache=None, batching="groups", stop_sequences=None,
-                 return_lengths=False, share_prefix=False, **unused):
+                 return_lengths=False, share_prefix=False, selection="torch", sync_every=1, **unused):
         """`llama_model.generate(inputs_embeds=..., ...)` as Chat.answer calls it (conversation.py:231-243; demo.py runs
         num_beams=5, do_sample=False): HIP prefill of `inputs_embeds` into a KV cache, then one decode step per token with
         HF's greedy / sampling / beam-search bookkeeping restated in stllm_amd/generation.py.  eos / pad default to the
@@ -802,7 +802,9 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
         to right-padded first.  With prefix_cache the prefix may hold one row shared by all prompts (N questions about one video) or one row per prompt.
         stop_sequences / return_lengths: see generation.generate (per-row stop; the number of generated tokens per row).
         share_prefix: rows with the same first positions (questions behind one prefix row, the beams of a prompt) read one physical copy of them instead of
-        owning one each (generation.generate).  Opt-in; needs use_cache."""
+        owning one each (generation.generate).  Opt-in; needs use_cache.
+        selection / sync_every: "device" selects every token with the project's own kernels and keeps the ids on the device (generation.generate;
+        DESIGN.md §4.2f).  Opt-in; "torch" (default) is the path as it always was."""
         from .. import generation
         if batching not in ("groups", "ragged"):
             raise ValueError(f"generate(batching={batching!r}): 'groups' or 'ragged'")
@@ -835,7 +837,7 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
                                        repetition_penalty=repetition_penalty, length_penalty=length_penalty,
                                        stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                        use_cache=use_cache, generator=generator, prefix=prefix_cache, lengths=lengths,
-                                       stop_sequences=stop_sequences, return_lengths=return_lengths, share_prefix=share_prefix)
+                                       stop_sequences=stop_sequences, return_lengths=return_lengths, share_prefix=share_prefix, selection=selection, sync_every=sync_every)
         if attention_mask is not None and inputs_embeds.shape[0] > 1:
             if prefix_cache is not None and not bool(hip.host_mask(attention_mask).to(torch.bool).all()):
                 raise NotImplementedError("generate(prefix_cache=...) with a padded batch: a prefix serves equal-length prompts only")
@@ -856,7 +858,7 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
                     emb = torch.stack([inputs_embeds[b, m.shape[1] - n:] if left[b] else inputs_embeds[b, :n] for b in rows], dim=0)
                     ids = self.generate(inputs_embeds=emb, max_new_tokens=max_new_tokens, num_beams=num_beams, do_sample=do_sample, stopping_criteria=stopping_criteria,
                                         use_cache=use_cache, min_length=min_length, top_p=top_p, repetition_penalty=repetition_penalty, length_penalty=length_penalty,
-                                        temperature=temperature, eos_token_id=eos_token_id, pad_token_id=pad_token_id, generator=generator, share_prefix=share_prefix)
+                                        temperature=temperature, eos_token_id=eos_token_id, pad_token_id=pad_token_id, generator=generator, share_prefix=share_prefix, selection=selection, sync_every=sync_every)
                     for j, b in enumerate(rows):
                         outs[b] = ids[j]
                 width = max(o.shape[0] for o in outs)
@@ -869,7 +871,7 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
                                    repetition_penalty=repetition_penalty, length_penalty=length_penalty,
                                    stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                    use_cache=use_cache, generator=generator, prefix=prefix_cache, stop_sequences=stop_sequences,
-                                   return_lengths=return_lengths, share_prefix=share_prefix)
+                                   return_lengths=return_lengths, share_prefix=share_prefix, selection=selection, sync_every=sync_every)
 
     @classmethod
     def get_state_dict(cls, path, prefix="pytorch_model"):

@@ -21,7 +21,15 @@ ap.add_argument("--questions", default="", help="L1,L2,...: N questions of these
                                                 "batch against one generate() per question (what a padded batch behind a prefix costs without the ragged cache)")
 ap.add_argument("--share-prefix", action="store_true", help="with --questions or --beams: generate(share_prefix=True) against share_prefix=False (private copies), "
                                                           "alternating; tokens/s and peak memory_allocated of both")
-ap.add_argument("--beams", type=int, default=0, help="with --share-prefix: one prompt of --prefix-len + 24 positions, this many beams (5 = demo.py)")
+ap.add_argument("--beams", type=int, default=0, help="with --share-prefix: one prompt of --prefix-len + 24 positions, this many beams (5 = demo.py); "
+                                                    "with --generate: num_beams of one prompt")
+ap.add_argument("--generate", type=int, default=0, help="N: end-to-end generate() of N new tokens per row behind a 576-position prompt (--rows prompts, or one prompt x --beams), "
+                                                       "tokens/s, and the selection step alone in us by device events, on the logits of that prompt")
+ap.add_argument("--selection", choices=["torch", "device", "both"], default="both", help="with --generate: the selection mode; 'both' alternates them, 3 repeats each")
+ap.add_argument("--sample", action="store_true", help="with --generate: top-p sampling (top_p 0.9, temperature 0.8) instead of greedy search")
+ap.add_argument("--cases", default="", help="with --generate: several workloads in one process (one model build), e.g. g1,g5,g16,s1,s16,b5 — g / s = greedy / sampled "
+                                            "rows, b = beams of one prompt; default: the one case --rows / --sample / --beams describe")
+ap.add_argument("--sync-every", type=int, default=1, help="with --generate, selection 'device': generate(sync_every=K)")
 ap.add_argument("--prefix-len", type=int, default=576, help="positions of the shared prefix of --share-prefix")
 args = ap.parse_args()
 torch.set_grad_enabled(False)
@@ -138,6 +146,78 @@ def share_prefix_e2e(lens, beams):
               f"(runs {' '.join(f'{x * 1e3:.1f}' for x in ts)}), peak memory above the model + prefix {peak[share] / 1e6:.0f} MB", flush=True)
 
 
+def generate_e2e(n_new, R, nb, sample):
+    """generate() end to end with torch / device selection, alternating, 3 repeats each behind one warm-up each; EOS disabled so that every run emits the
+    same number of ids; repetition penalty 1.5 as Chat.answer forces it.  Then the selection step alone on this prompt's first logits: the torch chain
+    generate() runs today against the kernel, 50 launches each between two device events."""
+    from stllm_amd import generation as G
+    B = 1 if nb else R
+    emb = torch.randn(B, S, 4096, device=dev) * 0.02
+    kw = dict(inputs_embeds=emb, max_new_tokens=n_new, eos_token_id=None, repetition_penalty=1.5, num_beams=max(nb, 1))
+    if sample:
+        kw.update(do_sample=True, top_p=0.9, temperature=0.8)
+    modes = ["torch", "device"] if args.selection == "both" else [args.selection]
+    what = f"{nb} beams" if nb else f"{R} rows, {'sample' if sample else 'greedy'}"
+    res = {}
+    for rep in range(4):
+        for mode in modes:
+            extra = dict(selection=mode, sync_every=args.sync_every) if mode == "device" else {}
+            gen = torch.Generator(device=dev).manual_seed(rep) if sample else None
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = model.generate(generator=gen, **kw, **extra)
+            torch.cuda.synchronize()
+            res.setdefault(mode, []).append(time.perf_counter() - t0)
+            assert out.shape[1] == n_new
+    rows = B * max(nb, 1)
+    for mode, ts in res.items():
+        t = sorted(ts[1:])[1]
+        print(f"generate ({what}, weights {args.weights}, {n_new} new tokens, selection {mode}{f', sync_every {args.sync_every}' if mode == 'device' else ''}): "
+              f"median {t * 1e3:.1f} ms = {t / n_new * 1e3:.3f} ms/token = {B * n_new / t:.1f} tok/s (runs {' '.join(f'{x * 1e3:.1f}' for x in ts[1:])}; warm-up {ts[0] * 1e3:.1f})", flush=True)
+    # the selection step alone, same logits for both: a padded-row view as logits_from returns it, 40 previous ids
+    _, h16 = lm.prefill(emb, None, cache=lm.new_cache(B, S, dev))
+    logits = model.logits_from(h16.view(B, S, -1)[:, -1].contiguous(), B, 1)[:, 0]
+    if nb:
+        logits = logits.repeat_interleave(nb, dim=0)
+    V = logits.shape[1]
+    prev = torch.randint(0, V, (rows, 64), device=dev, dtype=torch.int32)
+    ids, n_prev = prev[:, :40].long(), 40
+    bs = torch.linspace(0, -3, rows, device=dev)
+    out, u = torch.empty(rows, dtype=torch.int32, device=dev), torch.rand(rows, device=dev)
+
+    def torch_chain():
+        if nb:
+            lp = G._process_logits(logits.log_softmax(dim=-1), ids, n_prev, 1.5, 0, 2)
+            return torch.topk((lp + bs[:, None]).view(B, nb * V), 2 * nb, dim=1, largest=True, sorted=True)
+        sc = G._process_logits(logits, ids, n_prev, 1.5, 0, 2)
+        if sample:
+            return torch.multinomial(G._warp_logits(sc, 0.8, 0.9).softmax(dim=-1), num_samples=1)
+        return sc.argmax(dim=-1)
+
+    def kernel():
+        if nb:
+            return hip.beam_candidates(logits, bs, 2 * nb, prev=prev, n_prev=n_prev, penalty=1.5, eos_id=2)
+        return hip.select_tokens(logits, out, prev=prev, n_prev=n_prev, penalty=1.5, eos_id=2, sample=sample, temperature=0.8, top_p=0.9, u=u)
+    for name, f in (("torch chain", torch_chain), ("kernel", kernel)):
+        us = []
+        for _ in range(3):
+            for _ in range(5):
+                f()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(50):
+                f()
+            e1.record()
+            e1.synchronize()
+            us.append(e0.elapsed_time(e1) / 50 * 1e3)
+        print(f"selection step alone ({what}, V {V}, n_prev {n_prev}) [{name}]: {sorted(us)[1]:.1f} us (blocks {' '.join(f'{x:.1f}' for x in us)})", flush=True)
+
+
+if args.generate:
+    cases = args.cases.split(",") if args.cases else [f"b{args.beams}" if args.beams else f"{'s' if args.sample else 'g'}{args.rows}"]
+    for c in cases:
+        generate_e2e(args.generate, 1 if c[0] == "b" else int(c[1:]), int(c[1:]) if c[0] == "b" else 0, c[0] == "s")
+    sys.exit(0)
 if args.share_prefix:
     share_prefix_e2e([int(x) for x in args.questions.split(",")] if args.questions else [], args.beams)
     sys.exit(0)
