@@ -88,6 +88,23 @@ class Chat:
         lm.prefill(emb, None, cache=cache)
         return VideoPrefix(cache, emb.shape[1])
 
+    def _prompts(self, img_list, questions_ids, keep, prefix):
+        """conversation.py:213-253 for every question: its context embeddings [L, D], of which the last `keep` stay.  prefix = prefill_video(img_list)
+        and nothing truncated: only [BOS] + question, behind the prefix's cache (a truncated prompt would cut into the cached positions: whole prompts
+        then).  Returns (the embeddings per question, that cache | None)."""
+        embs = [self.get_context_emb_ids(img_list, q)[0][0] for q in questions_ids]
+        if prefix is not None and all(e.shape[0] <= keep for e in embs):
+            assert prefix.n_tokens == img_list[0].shape[1] == prefix.cache.len
+            return [e[prefix.n_tokens:] for e in embs], prefix.cache
+        return [e[max(0, e.shape[0] - keep):] for e in embs], None
+
+    def _decoded(self, tok):
+        """conversation.py:246-249: drop a leading <unk> (0), then a leading <s> (1); (text, ids)"""
+        for lead in (0, 1):
+            if tok.numel() and int(tok[0]) == lead:
+                tok = tok[1:]
+        return self.model.llama_tokenizer.decode(tok.tolist()), tok.cpu().numpy()
+
     def answer(self, img_list, question_ids, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9,
                repetition_penalty=1.0, length_penalty=1, temperature=1.0, max_length=2000, do_sample=False,
                stopping_criteria=None, instruction=False, prefix=None, share_prefix=False, **kw):
@@ -98,15 +115,12 @@ class Chat:
         repetition_penalty with 1.5 (conversation.py:219-220) whatever the caller passed; instruction=True keeps the argument.
         share_prefix: the beams read one copy of the prompt's (or the video prefix's) K / V rows (generate(share_prefix=True)).
         **kw reaches generate(): selection="device" (and sync_every=K) selects the tokens with the project's own kernels (generation.generate)."""
-        embs, att = self.get_context_emb_ids(img_list, question_ids)
         if not instruction:
             repetition_penalty = 1.5
-        begin = max(0, embs.shape[1] - (max_length - max_new_tokens))
-        embs = embs[:, begin:]
-        if prefix is not None and begin == 0:   # prefix = prefill_video(img_list): only [BOS] + question is new.  begin > 0: the truncation rule
-            assert prefix.n_tokens == img_list[0].shape[1] == prefix.cache.len   # would cut into the cached positions — the whole-prompt path below
-            embs = embs[:, prefix.n_tokens:]
-            kw = dict(kw, prefix_cache=prefix.cache)
+        (emb,), cache = self._prompts(img_list, [question_ids], max_length - max_new_tokens, prefix)
+        embs = emb[None]
+        if cache is not None:
+            kw = dict(kw, prefix_cache=cache)
         if stopping_criteria is None:
             stopping_criteria = self.stopping_criteria
         out = self.LLM.generate(inputs_embeds=embs, max_new_tokens=max_new_tokens, stopping_criteria=stopping_criteria,
@@ -114,12 +128,7 @@ class Chat:
                                 repetition_penalty=repetition_penalty, length_penalty=length_penalty, temperature=temperature,
                                 share_prefix=share_prefix, **kw)
         hip.gemm_workspace_check(embs.device, wait=True) if embs.is_cuda else None   # generate() synchronised on every token anyway
-        tok = out[0]
-        if tok.numel() and int(tok[0]) == 0:   # conversation.py:246-249
-            tok = tok[1:]
-        if tok.numel() and int(tok[0]) == 1:
-            tok = tok[1:]
-        return self.model.llama_tokenizer.decode(tok.tolist()), tok.cpu().numpy()
+        return self._decoded(out[0])
 
     def answer_many(self, img_list, questions_ids, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9,
                     repetition_penalty=1.0, length_penalty=1, temperature=1.0, max_length=2000, do_sample=False,
@@ -129,21 +138,14 @@ class Chat:
         prefill_video(img_list) result — the video is prefilled once, forked to the N rows, and only [BOS] + question runs per row.  Returns one
         (text, ids) pair per question, each what answer() returns for that question alone.  share_prefix: the N rows (and their beams) read the prefilled video
         where it is instead of a fork each (generate(share_prefix=True)).  **kw reaches generate(): selection="device", sync_every=K as in answer()."""
-        pairs = [self.get_context_emb_ids(img_list, q) for q in questions_ids]
         if not instruction:
             repetition_penalty = 1.5
-        keep = max_length - max_new_tokens
-        embs = [e[0, max(0, e.shape[1] - keep):] for e, _ in pairs]
-        if prefix is not None and all(e.shape[1] <= keep for e, _ in pairs):   # (a truncated prompt would cut into the cached positions: whole prompts below)
-            assert prefix.n_tokens == img_list[0].shape[1] == prefix.cache.len
-            embs = [e[prefix.n_tokens:] for e in embs]
-            kw = dict(kw, prefix_cache=prefix.cache)
-        lens = [e.shape[0] for e in embs]
-        batch = torch.zeros((len(embs), max(lens), embs[0].shape[-1]), dtype=embs[0].dtype, device=embs[0].device)
-        mask = torch.zeros((len(embs), max(lens)), dtype=torch.long)
-        for b, e in enumerate(embs):
-            batch[b, :lens[b]] = e
-            mask[b, :lens[b]] = 1
+        embs, cache = self._prompts(img_list, questions_ids, max_length - max_new_tokens, prefix)
+        if cache is not None:
+            kw = dict(kw, prefix_cache=cache)
+        lens = torch.tensor([e.shape[0] for e in embs])
+        batch = torch.nn.utils.rnn.pad_sequence(embs, batch_first=True)
+        mask = (torch.arange(int(lens.max()))[None, :] < lens[:, None]).long()
         if stop_sequences is None:
             stop_sequences = self.stopping_criteria[0].stops
         out, n_out = self.LLM.generate(inputs_embeds=batch, attention_mask=mask, max_new_tokens=max_new_tokens, stop_sequences=stop_sequences,
@@ -151,12 +153,4 @@ class Chat:
                                        repetition_penalty=repetition_penalty, length_penalty=length_penalty, temperature=temperature,
                                        return_lengths=True, share_prefix=share_prefix, **kw)
         hip.gemm_workspace_check(batch.device, wait=True) if batch.is_cuda else None
-        res = []
-        for row, n in zip(out, n_out):
-            tok = row[:n]
-            if tok.numel() and int(tok[0]) == 0:   # conversation.py:246-249
-                tok = tok[1:]
-            if tok.numel() and int(tok[0]) == 1:
-                tok = tok[1:]
-            res.append((self.model.llama_tokenizer.decode(tok.tolist()), tok.cpu().numpy()))
-        return res
+        return [self._decoded(row[:n]) for row, n in zip(out, n_out)]

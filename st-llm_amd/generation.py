@@ -26,6 +26,8 @@ the whole batch, which is wrong for more than one prompt).
 With `inputs_embeds` and no `input_ids` the sequences HF scores start empty, so every length below counts generated tokens
 only.  The prompt is prefilled ONCE and its cache rows are replicated to the beams (HF prefills num_beams identical copies).
 """
+import collections
+
 import torch
 
 
@@ -96,72 +98,67 @@ def _ends_in_stop(ids, stop_sequences):
     return hit
 
 
+# the sampling and stopping options of generate() (see its docstring) and their defaults, stated once: every public entry builds one Options from its keywords
+_DEFAULTS = dict(max_new_tokens=16, num_beams=1, do_sample=False, min_length=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0,
+                 stopping_criteria=None, eos_token_id=2, pad_token_id=0, use_cache=True, generator=None, stop_sequences=None, return_lengths=False,
+                 share_prefix=False, selection="torch", sync_every=1)
+Options = collections.namedtuple("Options", list(_DEFAULTS), defaults=list(_DEFAULTS.values()))
+
+
 class _CacheStepper:
     """next-token logits from the model: prefill once, then one decode step per token; rows can be re-ordered (beams)."""
 
-    def __init__(self, lm_wrapper, inputs_embeds, rows, max_new_tokens, use_cache=True, prefix=None, lengths=None, share_prefix=False):
+    def __init__(self, lm_wrapper, inputs_embeds, opts, prefix=None, lengths=None):
+        """prefix: a KVCache holding the prompts' first positions (a prefilled video; one row per prompt, or with `lengths` one row shared by all), left
+        as it was: the work happens on a fork (a copy per row) or, share_prefix, on a cache that reads it where it is (KVCache.share).
+        lengths: row b of the right-padded `inputs_embeds` holds lengths[b] tokens -> a ragged cache; the beams of a prompt inherit its length."""
         self.m, self.lm = lm_wrapper, lm_wrapper.model
-        self.use_cache = use_cache
-        if share_prefix and not use_cache:
-            raise ValueError("generate(share_prefix=True) needs use_cache: what is shared is the KV cache of the prompt's first positions")
+        self.use_cache, self.rep = opts.use_cache, opts.num_beams      # rep: beams per prompt
+        share, room = opts.share_prefix, opts.max_new_tokens
         emb = inputs_embeds.float()
         B, S, _ = emb.shape
-        self.rep = rows // B                      # beams per prompt
+        if share and not self.use_cache:
+            raise ValueError("generate(share_prefix=True) needs use_cache: what is shared is the KV cache of the prompt's first positions")
         if lengths is not None:
-            # ragged prompts: row b of the right-padded `inputs_embeds` holds lengths[b] tokens.  One prefill (or one extend behind the prefix) fills a ragged
-            # cache; the first logits are those of each prompt's LAST real token; the beams of a prompt are copies of its row and inherit its length.
-            if not use_cache:
+            if not self.use_cache:
                 raise ValueError("generate(lengths=...): ragged batches need use_cache")
             lengths = [int(n) for n in lengths]
             assert len(lengths) == B and all(1 <= n <= S for n in lengths)
-            if prefix is not None:
-                if prefix.batch not in (1, B):
-                    raise ValueError("generate(prefix=..., lengths=...): the prefix holds one row shared by every prompt, or one row per prompt")
-                # share_prefix: the rows READ the prefix where it is (KVCache.share) instead of owning a copy of it each
-                self.cache = prefix.share(rows=B, max_new=S + max_new_tokens) if share_prefix else prefix.fork(rows=B, max_len=prefix.len + S + max_new_tokens)
-                _, h16 = self.lm.extend(emb, self.cache, lengths=lengths)
-            else:
-                self.cache = self.lm.new_cache(B, S + max_new_tokens, emb.device)
-                mask = (torch.arange(S)[None, :] < torch.tensor(lengths)[:, None]).long()
-                _, h16 = self.lm.prefill(emb, mask, cache=self.cache)
-            last = h16.view(B, S, -1)[torch.arange(B), torch.tensor(lengths) - 1].contiguous()
-            logits = self.m.logits_from(last, B, 1)[:, 0]
-            if self.rep > 1:
-                if share_prefix and self.cache.base is None:
-                    raise NotImplementedError("generate(share_prefix=True, lengths=...) with beams needs prefix=: a ragged prompt cache cannot be a shared base")
-                self.cache = self.cache.share(rows=rows) if share_prefix else self.cache.fork(rows=rows)   # share: the same base, the question rows copied per beam
-                logits = logits.repeat_interleave(self.rep, dim=0)
-            self.logits = logits.float()
-        elif prefix is not None:
-            # `prefix`: a KVCache holding the prompt's first positions (a prefilled video); inputs_embeds is the rest.  The work happens on a fork
-            # — a copy of the prefix rows, made once per beam —, so the prefix itself stays as it was and serves the next call.
-            if not use_cache or prefix.batch != B:
-                raise ValueError("generate(prefix=...): needs use_cache and one prefix row per prompt")
-            self.cache = prefix.share(max_new=S + max_new_tokens) if share_prefix else prefix.fork(max_len=prefix.len + S + max_new_tokens)
-            _, h16 = self.lm.extend(emb, self.cache)
-            logits = self.m.logits_from(h16.view(B, S, -1)[:, -1].contiguous(), B, 1)[:, 0]
-            if self.rep > 1:
-                self.cache = self.cache.share(rows=rows) if share_prefix else self.cache.fork(rows=rows)
-                logits = logits.repeat_interleave(self.rep, dim=0)
-            self.logits = logits.float()
-        elif use_cache:
-            self.cache = self.lm.new_cache(B, S + max_new_tokens, emb.device)
-            _, h16 = self.lm.prefill(emb, None, cache=self.cache)
-            logits = self.m.logits_from(h16.view(B, S, -1)[:, -1].contiguous(), B, 1)[:, 0]
-            if self.rep > 1 and share_prefix:     # the prompt's cache is the base of its beams: never replicated, read once per step for all of them
-                self.cache = self.cache.share(rows=rows, max_new=max_new_tokens)
-                logits = logits.repeat_interleave(self.rep, dim=0)
-            elif self.rep > 1:                    # replicate the prompt's cache rows to the beams
-                big = self.lm.new_cache(rows, S + max_new_tokens, emb.device)
-                for dst, src in zip(big.qkv, self.cache.qkv):
-                    dst[:, :S] = src[:, :S].repeat_interleave(self.rep, dim=0)
-                big.len = self.cache.len
-                self.cache = big
-                logits = logits.repeat_interleave(self.rep, dim=0)
-            self.logits = logits.float()
-        else:
-            self.emb = emb.repeat_interleave(self.rep, dim=0)
+            if prefix is not None and prefix.batch not in (1, B):
+                raise ValueError("generate(prefix=..., lengths=...): the prefix holds one row shared by every prompt, or one row per prompt")
+            if share and prefix is None and self.rep > 1:
+                raise NotImplementedError("generate(share_prefix=True, lengths=...) with beams needs prefix=: a ragged prompt cache cannot be a shared base")
+        elif prefix is not None and (not self.use_cache or prefix.batch != B):
+            raise ValueError("generate(prefix=...): needs use_cache and one prefix row per prompt")
+
+        def per_beam(t):                          # row b -> rows [b * rep, (b + 1) * rep)
+            return t.repeat_interleave(self.rep, dim=0) if self.rep > 1 else t
+        if not self.use_cache:
+            self.emb = per_beam(emb)
             self.logits = self.m.forward(samples=None, inputs_embeds=self.emb).logits[:, -1].float()
+            return
+        # the cache of the B prompt rows, with room for the prompt and the new tokens ...
+        if prefix is None:
+            cache = self.lm.new_cache(B, S + room, emb.device)
+        elif share:
+            cache = prefix.share(rows=B, max_new=S + room)
+        else:
+            cache = prefix.fork(rows=B, max_len=prefix.len + S + room)
+        # ... filled in ONE pass: behind the prefix, or from position 0 (a right-padded mask makes the cache ragged)
+        if prefix is not None:
+            _, h16 = self.lm.extend(emb, cache, lengths=lengths)
+        else:
+            mask = None if lengths is None else (torch.arange(S)[None, :] < torch.tensor(lengths)[:, None]).long()
+            _, h16 = self.lm.prefill(emb, mask, cache=cache)
+        # the first logits are those of every prompt's LAST real token
+        h16 = h16.view(B, S, -1)
+        last = h16[:, -1] if lengths is None else h16[torch.arange(B), torch.tensor(lengths) - 1]
+        logits = self.m.logits_from(last.contiguous(), B, 1)[:, 0]
+        if self.rep > 1:
+            # the beams of a prompt: copies of its cache row (fork), or, share_prefix, readers of ONE base — the prefix when there is one (the rows
+            # behind it are copied per beam), else the prompt's own cache, never replicated; max_new counts the positions behind that base
+            cache = cache.share(rows=B * self.rep, max_new=cache.max_len - (cache.base_len or cache.len)) if share else cache.fork(rows=B * self.rep)
+        self.cache, self.logits = cache, per_beam(logits).float()
 
     def advance(self, next_tokens, beam_idx=None, on_device=False):
         """append `next_tokens` [rows] (after re-ordering the rows by `beam_idx`) and compute the next logits.
@@ -212,45 +209,70 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
     sync_every: "device", num_beams == 1 only — the host reads `unfinished` back every sync_every-th step instead of every step; finished rows emit
     pad_token_id meanwhile, and the result is cut where every row had finished: the same ids.  A `stopping_criteria` callable needs the ids of every
     step and forces 1."""
-    B = inputs_embeds.shape[0]
-    dev = inputs_embeds.device
-    stop_sequences = list(stop_sequences) if stop_sequences else None
-    if selection not in ("torch", "device"):
-        raise ValueError(f"generate(selection={selection!r}): 'torch' or 'device'")
-    on_device = selection == "device"
-    if on_device and num_beams == 1:
-        return _generate_device(lm_wrapper, inputs_embeds, max_new_tokens, do_sample, min_length, top_p, temperature, repetition_penalty, stopping_criteria,
-                                eos_token_id, pad_token_id, use_cache, generator, prefix, lengths, stop_sequences, return_lengths, share_prefix, sync_every)
-    if num_beams == 1:
-        st = _CacheStepper(lm_wrapper, inputs_embeds, B, max_new_tokens, use_cache, prefix, lengths, share_prefix)
-        ids = torch.zeros((B, 0), dtype=torch.long, device=dev)
-        unfinished = torch.ones(B, dtype=torch.long, device=dev)
-        n_gen = torch.zeros(B, dtype=torch.long, device=dev)
-        while True:
-            scores = _process_logits(st.logits.to(dev), ids, ids.shape[1], repetition_penalty, min_length, eos_token_id)
-            if do_sample:
-                probs = _warp_logits(scores, temperature, top_p).softmax(dim=-1)
-                nxt = torch.multinomial(probs, num_samples=1, generator=generator).squeeze(1)
-            else:
-                nxt = scores.argmax(dim=-1)
-            if eos_token_id is not None or stop_sequences:
-                nxt = nxt * unfinished + pad_token_id * (1 - unfinished)
-            ids = torch.cat([ids, nxt[:, None]], dim=-1)
-            n_gen = n_gen + unfinished
-            if eos_token_id is not None:
-                unfinished = unfinished * (nxt != eos_token_id).long()
-            if stop_sequences:
-                unfinished = unfinished * (~_ends_in_stop(ids, stop_sequences)).long()
-            if unfinished.max() == 0 or _stop(stopping_criteria, ids, scores) or ids.shape[1] >= max_new_tokens:
-                break
-            st.advance(nxt)
-        _check_exchanges(dev)
-        return (ids, n_gen.tolist()) if return_lengths else ids
+    opts = Options(max_new_tokens=max_new_tokens, num_beams=num_beams, do_sample=do_sample, min_length=min_length, top_p=top_p, temperature=temperature,
+                   repetition_penalty=repetition_penalty, length_penalty=length_penalty, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
+                   pad_token_id=pad_token_id, use_cache=use_cache, generator=generator, stop_sequences=stop_sequences, return_lengths=return_lengths,
+                   share_prefix=share_prefix, selection=selection, sync_every=sync_every)
+    return _generate(lm_wrapper, inputs_embeds, opts, prefix, lengths)
 
-    if do_sample:
+
+def _generate(lm_wrapper, inputs_embeds, opts, prefix=None, lengths=None):
+    """generate() on an Options object: the three decode loops.  They stay apart — the torch loop is what the device loop is tested against — and share
+    their head (_CacheStepper) and tail (_finish) only."""
+    if opts.selection not in ("torch", "device"):
+        raise ValueError(f"generate(selection={opts.selection!r}): 'torch' or 'device'")
+    opts = opts._replace(stop_sequences=list(opts.stop_sequences) if opts.stop_sequences else None)
+    if opts.num_beams > 1:
+        return _generate_beams(lm_wrapper, inputs_embeds, opts, prefix, lengths)
+    loop = _generate_device if opts.selection == "device" else _generate_torch
+    return loop(lm_wrapper, inputs_embeds, opts, prefix, lengths)
+
+
+def _finish(ids, n_gen, opts):
+    """the common tail of the loops.  Every token was read back on the host, so the stream is idle: a timed-out split-K exchange anywhere in this
+    generate() call must not come back as plausible-looking ids.  n_gen: the number of generated tokens per row, returned on request."""
+    if ids.device.type == "cuda":
+        from . import hip
+        hip.gemm_workspace_check(ids.device, wait=True)
+    return (ids, n_gen) if opts.return_lengths else ids
+
+
+def _generate_torch(lm_wrapper, inputs_embeds, o, prefix, lengths):
+    """greedy search / sampling with torch operators"""
+    B, dev = inputs_embeds.shape[0], inputs_embeds.device
+    st = _CacheStepper(lm_wrapper, inputs_embeds, o, prefix, lengths)
+    ids = torch.zeros((B, 0), dtype=torch.long, device=dev)
+    unfinished = torch.ones(B, dtype=torch.long, device=dev)
+    n_gen = torch.zeros(B, dtype=torch.long, device=dev)
+    while True:
+        scores = _process_logits(st.logits.to(dev), ids, ids.shape[1], o.repetition_penalty, o.min_length, o.eos_token_id)
+        if o.do_sample:
+            probs = _warp_logits(scores, o.temperature, o.top_p).softmax(dim=-1)
+            nxt = torch.multinomial(probs, num_samples=1, generator=o.generator).squeeze(1)
+        else:
+            nxt = scores.argmax(dim=-1)
+        if o.eos_token_id is not None or o.stop_sequences:
+            nxt = nxt * unfinished + o.pad_token_id * (1 - unfinished)
+        ids = torch.cat([ids, nxt[:, None]], dim=-1)
+        n_gen = n_gen + unfinished
+        if o.eos_token_id is not None:
+            unfinished = unfinished * (nxt != o.eos_token_id).long()
+        if o.stop_sequences:
+            unfinished = unfinished * (~_ends_in_stop(ids, o.stop_sequences)).long()
+        if unfinished.max() == 0 or _stop(o.stopping_criteria, ids, scores) or ids.shape[1] >= o.max_new_tokens:
+            break
+        st.advance(nxt)
+    return _finish(ids, n_gen.tolist() if o.return_lengths else None, o)
+
+
+def _generate_beams(lm_wrapper, inputs_embeds, opts, prefix, lengths):
+    """beam search; selection="device" takes the candidates of every step from hip.beam_candidates, the scorer is the same"""
+    if opts.do_sample:
         raise NotImplementedError("beam-sample is not used by the reference (demo: num_beams=5, do_sample=False)")
-    nb = num_beams
-    st = _CacheStepper(lm_wrapper, inputs_embeds, B * nb, max_new_tokens, use_cache, prefix, lengths, share_prefix)
+    B, dev, nb, on_device = inputs_embeds.shape[0], inputs_embeds.device, opts.num_beams, opts.selection == "device"
+    max_new_tokens, min_length, repetition_penalty, length_penalty = opts.max_new_tokens, opts.min_length, opts.repetition_penalty, opts.length_penalty
+    eos_token_id, pad_token_id, stop_sequences, stopping_criteria = opts.eos_token_id, opts.pad_token_id, opts.stop_sequences, opts.stopping_criteria
+    st = _CacheStepper(lm_wrapper, inputs_embeds, opts, prefix, lengths)
     ids = torch.zeros((B * nb, 0), dtype=torch.long, device=dev)
     beam_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
     beam_scores[:, 1:] = -1e9
@@ -260,7 +282,8 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
     while True:
         cur_len = ids.shape[1]
         if on_device:
-            cs, ct, cb = _device_candidates(st.logits, ids, beam_scores, B, nb, repetition_penalty, cur_len < min_length, eos_token_id)
+            cs, ct, cb = _device_candidates(st.logits, ids, beam_scores, B, nb, repetition_penalty=repetition_penalty, suppress_eos=cur_len < min_length,
+                                            eos_token_id=eos_token_id)
         else:
             logp = st.logits.to(dev).log_softmax(dim=-1)
             logp = _process_logits(logp, ids, cur_len, repetition_penalty, min_length, eos_token_id)
@@ -322,11 +345,10 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
         res[b, :len(o)] = o
         if len(o) < sent_max:
             res[b, len(o)] = eos_token_id
-    _check_exchanges(dev)
-    return (res, [min(len(o) + 1, sent_max) for o in out]) if return_lengths else res
+    return _finish(res, [min(len(o) + 1, sent_max) for o in out], opts)
 
 
-def _device_candidates(logits, ids, beam_scores, B, nb, repetition_penalty, suppress_eos, eos_token_id):
+def _device_candidates(logits, ids, beam_scores, B, nb, *, repetition_penalty, suppress_eos, eos_token_id):
     """selection="device": what `topk` over the nb * V scores of a prompt returns, from hip.beam_candidates.  Every beam row gives its k = 2 * nb best
     (score descending, token ascending); ONE device -> host copy brings the nb * k (score, token) pairs of every prompt over, and the host merges them by
     (score descending, beam * V + token ascending).  Returns CPU tensors (scores f32, tokens, beams) [B, 2 * nb]."""
@@ -348,26 +370,27 @@ def _device_candidates(logits, ids, beam_scores, B, nb, repetition_penalty, supp
     return cs, ct, cb
 
 
-def _generate_device(lm_wrapper, inputs_embeds, max_new_tokens, do_sample, min_length, top_p, temperature, repetition_penalty, stopping_criteria,
-                     eos_token_id, pad_token_id, use_cache, generator, prefix, lengths, stop_sequences, return_lengths, share_prefix, sync_every):
+def _generate_device(lm_wrapper, inputs_embeds, opts, prefix, lengths):
     """greedy search / sampling of generate(selection="device"): one hip.select_tokens launch per step, the ids stay on the device"""
     from . import hip
     B, dev = inputs_embeds.shape[0], inputs_embeds.device
-    st = _CacheStepper(lm_wrapper, inputs_embeds, B, max_new_tokens, use_cache, prefix, lengths, share_prefix)
+    max_new_tokens, min_length, do_sample, generator, stopping_criteria = opts.max_new_tokens, opts.min_length, opts.do_sample, opts.generator, opts.stopping_criteria
+    eos_token_id, pad_token_id, stop_sequences = opts.eos_token_id, opts.pad_token_id, opts.stop_sequences
+    st = _CacheStepper(lm_wrapper, inputs_embeds, opts, prefix, lengths)
     ids = torch.full((B, max_new_tokens), pad_token_id, dtype=torch.int32, device=dev)
     track = eos_token_id is not None or bool(stop_sequences)     # rows can finish: the kernel keeps `unfinished`
     unfinished = torch.ones(B, dtype=torch.int32, device=dev)
     n_gen = torch.zeros(B, dtype=torch.int32, device=dev)
-    every = 1 if stopping_criteria is not None else max(1, int(sync_every))
+    every = 1 if stopping_criteria is not None else max(1, int(opts.sync_every))
     nxt = torch.empty(B, dtype=torch.int32, device=dev)
     u, t = None, 0
     while True:
         n_gen += unfinished
         if do_sample:
             u = torch.rand(B, generator=generator, device=generator.device if generator is not None else dev).to(dev)
-        hip.select_tokens(st.logits, ids[:, t], prev=ids, n_prev=t, penalty=repetition_penalty,
+        hip.select_tokens(st.logits, ids[:, t], prev=ids, n_prev=t, penalty=opts.repetition_penalty,
                           suppress_eos=eos_token_id is not None and t < min_length, eos_id=eos_token_id, pad_id=pad_token_id, sample=do_sample,
-                          temperature=temperature, top_p=top_p, u=u, unfinished=unfinished if track else None)
+                          temperature=opts.temperature, top_p=opts.top_p, u=u, unfinished=unfinished if track else None)
         t += 1
         if stop_sequences:
             unfinished *= (~_ends_in_stop(ids[:, :t], stop_sequences)).to(torch.int32)
@@ -381,14 +404,4 @@ def _generate_device(lm_wrapper, inputs_embeds, max_new_tokens, do_sample, min_l
         st.advance(nxt, on_device=True)
     n_host = n_gen.tolist()
     n = t if stopping_criteria is not None else max(n_host)      # sync_every > 1 runs past the step at which every row had finished: cut there
-    out = ids[:, :n].long()
-    _check_exchanges(dev)
-    return (out, n_host) if return_lengths else out
-
-
-def _check_exchanges(dev):
-    """every token was read back on the host, so the stream is idle: a timed-out split-K exchange anywhere in this generate()
-    call must not come back as plausible-looking ids"""
-    if torch.device(dev).type == "cuda":
-        from . import hip
-        hip.gemm_workspace_check(dev, wait=True)
+    return _finish(ids[:, :n].long(), n_host, opts)

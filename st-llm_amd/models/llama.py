@@ -164,6 +164,16 @@ class KVCache:
         self.len = self.base_len
         self.lens = None
 
+    def flat(self, li):
+        """layer li's own buffer as 2-D rows [batch * capacity, 3 * hidden]: row (b, local position s) at b * capacity + s"""
+        buf = self.qkv[li]
+        return buf.view(buf.shape[0] * buf.shape[1], buf.shape[2])
+
+    def kv(self, li):
+        """(k, v, strides): the K and V columns of flat(li) and their (batch stride, row stride) in elements — what the attention entry points take"""
+        D, rows = self.hidden, self.flat(li)
+        return rows[:, D:2 * D], rows[:, 2 * D:], (self.qkv[li].shape[1] * 3 * D, 3 * D)
+
     def set_lens(self, lens):
         """per-row lengths (a list of `batch` ints) -> ragged; None, or all rows equal -> uniform"""
         if lens is None or len(set(lens)) <= 1:
@@ -400,16 +410,10 @@ class LlamaModel(nn.Module):
         entry point is tested against (-m gpu: bit-identical) and as the body the test-only CPU contract backend runs."""
         D, H = self.config.hidden_size, self.config.num_attention_heads
         hd = D // H
-        if cache is None:
-            strides = None
+        strides = None if cache is None else cache.kv(0)[2]
 
-            def qkv_to(li):
-                return {}
-        else:  # the cache buffer is the GEMM's output: rows (b, s) at b*max_len + s
-            strides = (cache.max_len * 3 * D, 3 * D)
-
-            def qkv_to(li):
-                return dict(out=cache.qkv[li].view(B * cache.max_len, 3 * D), M=B * S, o_rows=(S, cache.max_len * 3 * D))
+        def qkv_to(li):   # the cache buffer is the GEMM's output: rows (b, s) at b*max_len + s
+            return {} if cache is None else dict(out=cache.flat(li), M=B * S, o_rows=(S, strides[0]))
 
         def attn(li, qkv):
             return hip.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B=B, H=H, Sq=S, Skv=S, D=hd,
@@ -471,16 +475,16 @@ class LlamaModel(nn.Module):
         run, and the one the test-only CPU contract backend runs"""
         D, H = self.config.hidden_size, self.config.num_attention_heads
         hd = D // H
-        ML3 = cache.max_len * 3 * D
         kv = {"kv_len": kv_len} if kv_len is not None else {}
+        strides = cache.kv(0)[2]
 
         def qkv_to(li):   # row (b, s) of the suffix at b * max_len + P + s
-            return dict(out=cache.qkv[li].view(B * cache.max_len, 3 * D)[P:], M=B * S, o_rows=(S, ML3))
+            return dict(out=cache.flat(li)[P:], M=B * S, o_rows=(S, strides[0]))
 
         def attn(li, new):
-            full = cache.qkv[li].view(B * cache.max_len, 3 * D)
-            return hip.attention(new[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=S, Skv=P + S, D=hd, scale=hd ** -0.5, causal=True,
-                                 q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D), v_strides=(ML3, 3 * D), q_off=P, **kv)
+            k, v, _ = cache.kv(li)
+            return hip.attention(new[:, :D], k, v, B=B, H=H, Sq=S, Skv=P + S, D=hd, scale=hd ** -0.5, causal=True,
+                                 q_strides=strides, k_strides=strides, v_strides=strides, q_off=P, **kv)
         proj = gemm_proj(layers, dt, True)
         for li, pk in enumerate(layers):
             decoder_layer(self, dt, x, pk, li, proj=proj, qkv_to=qkv_to, attn=attn, rope=(cos, sin), rope_seq=S)
@@ -493,20 +497,18 @@ class LlamaModel(nn.Module):
         off + S_b suffix keys (causal with the query offset `off`)."""
         D, H = self.config.hidden_size, self.config.num_attention_heads
         hd = D // H
-        base, P = cache.base, cache.base_len
+        P = cache.base_len
         off = pos - P
-        cap = cache.qkv[0].shape[1]
         dev = x.device
         sfx_len = None if lengths is None else hip.h2d(torch.tensor([off + n for n in lengths], dtype=torch.int32), dev)
         dense = torch.empty((B * S, 3 * D), device=dev, dtype=dt)
 
         def attn(li, dense):
             cache.qkv[li][:, off:off + S].copy_(dense.view(B, S, 3 * D))
-            bq = base.qkv[li].view(base.batch * base.max_len, 3 * D)
-            sq = cache.qkv[li].view(B * cap, 3 * D)
-            return hip.attention_shared(dense[:, :D], bq[:, D:2 * D], bq[:, 2 * D:], sq[:, D:2 * D], sq[:, 2 * D:], B=B, G=base.batch, H=H, Sq=S, P=P, D=hd,
+            (kp, vp, kp_strides), (ks, vs, ks_strides) = cache.base.kv(li), cache.kv(li)
+            return hip.attention_shared(dense[:, :D], kp, vp, ks, vs, B=B, G=cache.base.batch, H=H, Sq=S, P=P, D=hd,
                                         scale=hd ** -0.5, max_sfx=off + S, sfx_len=sfx_len, sfx_q_off=off, causal=True, q_strides=(S * 3 * D, 3 * D),
-                                        kp_strides=(base.max_len * 3 * D, 3 * D), ks_strides=(cap * 3 * D, 3 * D))
+                                        kp_strides=kp_strides, ks_strides=ks_strides)
         proj = gemm_proj(layers, dt, True)
         for li, pk in enumerate(layers):
             decoder_layer(self, dt, x, pk, li, proj=proj, qkv_to=lambda li: {"out": dense}, attn=attn, rope=(cos, sin), rope_seq=S)
@@ -681,27 +683,22 @@ class LlamaModel(nn.Module):
             # shared base (rg: decode_step's tables in LOCAL positions): append to the cache's own rows, then every group of rows reads the base's P keys
             # once and each row its own suffix (bf16 / fp16: the shared-prefix decode kernels, 2 launches; fp32: the vector kernel).  No other kernel runs
             # in their place: an unsupported head_dim is an error of the C entry point
-            base, cap = cache.base, cache.qkv[li_].shape[1]
             hip.kv_append_rows(row, cache.qkv[li_], rg["pos"])
-            bq = base.qkv[li_].view(base.batch * base.max_len, 3 * D)
-            sq = cache.qkv[li_].view(B * cap, 3 * D)
-            return hip.attention_shared(row[:, :D], bq[:, D:2 * D], bq[:, 2 * D:], sq[:, D:2 * D], sq[:, 2 * D:], B=B, G=base.batch, H=H, Sq=1,
+            (kp, vp, kp_strides), (ks, vs, ks_strides) = cache.base.kv(li_), cache.kv(li_)
+            return hip.attention_shared(row[:, :D], kp, vp, ks, vs, B=B, G=cache.base.batch, H=H, Sq=1,
                                         P=cache.base_len, D=hd, scale=hd ** -0.5, max_sfx=rg["max_kv"], sfx_len=rg["kv_len"], q_strides=(3 * D, 3 * D),
-                                        kp_strides=(base.max_len * 3 * D, 3 * D), ks_strides=(cap * 3 * D, 3 * D))
-        ML3 = cache.max_len * 3 * D
-        full = cache.qkv[li_].view(B * cache.max_len, 3 * D)
+                                        kp_strides=kp_strides, ks_strides=ks_strides)
+        k, v, strides = cache.kv(li_)
         if rg is None:
-            return hip.attention(row[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=1, Skv=pos + 1, D=hd,
-                                 scale=hd ** -0.5, causal=False, q_strides=(ML3, 3 * D), k_strides=(ML3, 3 * D),
-                                 v_strides=(ML3, 3 * D))
+            return hip.attention(row[:, :D], k, v, B=B, H=H, Sq=1, Skv=pos + 1, D=hd,
+                                 scale=hd ** -0.5, causal=False, q_strides=strides, k_strides=strides, v_strides=strides)
         # the cache rows behind a row's length are UNINITIALISED memory.  The ragged decode kernels and the fp32 vector kernel bound their key loops by
         # kv_len and never read them; the 16-bit tile kernels load whole key tiles up to Skv and mask the scores only (0 x NaN would reach the output)
         if row.dtype != torch.float32 and (hd != 128 or not hip._decode_attn):
             raise NotImplementedError("ragged decode step in bf16 / fp16 needs the ragged decode attention kernels (head_dim 128, hip._decode_attn on)")
         hip.kv_append_rows(row, cache.qkv[li_], rg["pos"])
-        return hip.attention(row[:, :D], full[:, D:2 * D], full[:, 2 * D:], B=B, H=H, Sq=1, Skv=rg["max_kv"], D=hd,
-                             scale=hd ** -0.5, causal=False, kv_len=rg["kv_len"], q_strides=(3 * D, 3 * D), k_strides=(ML3, 3 * D),
-                             v_strides=(ML3, 3 * D))
+        return hip.attention(row[:, :D], k, v, B=B, H=H, Sq=1, Skv=rg["max_kv"], D=hd,
+                             scale=hd ** -0.5, causal=False, kv_len=rg["kv_len"], q_strides=(3 * D, 3 * D), k_strides=strides, v_strides=strides)
 
     def new_cache(self, batch, max_len, device):
         return KVCache(len(self.layers), batch, max_len, self.config.hidden_size, runtime.compute_dtype(), device)

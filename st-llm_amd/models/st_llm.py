@@ -646,6 +646,17 @@ class STLLMLlamaModel(LlamaModel):
         return outputs, loss_rows.mean(), labels
 
 
+def _prompt_spans(attention_mask, batching):
+    """(index of the first token, number of tokens) of every row of a padded batch, from the host copy of the mask: rows are left- or right-padded"""
+    spans = []
+    for row in hip.host_mask(attention_mask).to(torch.bool):
+        first, n = int(row.long().argmax()), int(row.sum())
+        if not bool(row[first:first + n].all()):
+            raise NotImplementedError(f"generate(batching={batching!r}): the tokens of a row must be contiguous (left- or right-padded)")
+        spans.append((first, n))
+    return spans
+
+
 @registry.register_model("st_llm_hf")
 class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
     config_class = StllmConfig
@@ -808,70 +819,52 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
         from .. import generation
         if batching not in ("groups", "ragged"):
             raise ValueError(f"generate(batching={batching!r}): 'groups' or 'ragged'")
+        opts = generation.Options(max_new_tokens=max_new_tokens, num_beams=num_beams, do_sample=do_sample, min_length=min_length, top_p=top_p,
+                                  temperature=temperature, repetition_penalty=repetition_penalty, length_penalty=length_penalty,
+                                  stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id, use_cache=use_cache,
+                                  generator=generator, stop_sequences=stop_sequences, return_lengths=return_lengths, share_prefix=share_prefix,
+                                  selection=selection, sync_every=sync_every)
+        B, S = inputs_embeds.shape[:2]
+        spans = [(0, S)] * B if attention_mask is None or (batching == "groups" and B == 1) else _prompt_spans(attention_mask, batching)
+        lengths = [n for _, n in spans]
+        padded = lengths != [S] * B
         if batching == "ragged":
-            B, S = inputs_embeds.shape[:2]
-            lengths = None
-            if attention_mask is not None:
-                m = hip.host_mask(attention_mask).to(torch.bool)
-                lengths = m.sum(dim=1).tolist()
-                if min(lengths) < 1:
-                    raise ValueError("generate(batching='ragged'): every prompt needs at least one token")
-                if not bool(m.all()):
-                    right = m.long()
-                    right = bool((right[:, 1:] <= right[:, :-1]).all())
-                    if not right:   # left-padded rows (or a mix): shift every row's tokens to the front — positions count real tokens only
-                        emb = torch.zeros_like(inputs_embeds)
-                        for b, n in enumerate(lengths):
-                            first = int(m[b].long().argmax())
-                            if not bool(m[b, first:first + n].all()):
-                                raise NotImplementedError("generate(batching='ragged'): the tokens of a row must be contiguous (left- or right-padded)")
-                            emb[b, :n] = inputs_embeds[b, first:first + n]
-                        inputs_embeds = emb
-                    inputs_embeds = inputs_embeds[:, :max(lengths)]
-                if len(set(lengths)) == 1 and lengths[0] == inputs_embeds.shape[1] and (prefix_cache is None or prefix_cache.batch == B):
-                    lengths = None   # equal lengths: the plain batched call
-            if lengths is None and prefix_cache is not None and prefix_cache.batch != B:
-                lengths = [inputs_embeds.shape[1]] * B   # one shared prefix row, equal-length questions: the ragged stepper forks it per prompt
-            return generation.generate(self, inputs_embeds, max_new_tokens=max_new_tokens, num_beams=num_beams, do_sample=do_sample,
-                                       min_length=min_length, top_p=top_p, temperature=temperature,
-                                       repetition_penalty=repetition_penalty, length_penalty=length_penalty,
-                                       stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                                       use_cache=use_cache, generator=generator, prefix=prefix_cache, lengths=lengths,
-                                       stop_sequences=stop_sequences, return_lengths=return_lengths, share_prefix=share_prefix, selection=selection, sync_every=sync_every)
-        if attention_mask is not None and inputs_embeds.shape[0] > 1:
-            if prefix_cache is not None and not bool(hip.host_mask(attention_mask).to(torch.bool).all()):
+            if min(lengths) < 1:
+                raise ValueError("generate(batching='ragged'): every prompt needs at least one token")
+            if any(first for first, _ in spans):   # left-padded rows (or a mix): shift every row's tokens to the front — positions count real tokens only
+                emb = torch.zeros_like(inputs_embeds)
+                for b, (first, n) in enumerate(spans):
+                    emb[b, :n] = inputs_embeds[b, first:first + n]
+                inputs_embeds = emb
+            if padded:
+                inputs_embeds = inputs_embeds[:, :max(lengths)]
+            # equal lengths: the plain batched call — unless ONE prefix row serves every prompt, which the ragged stepper forks (or shares) per prompt
+            if len(set(lengths)) == 1 and lengths[0] == inputs_embeds.shape[1] and (prefix_cache is None or prefix_cache.batch == B):
+                lengths = None
+            return generation._generate(self, inputs_embeds, opts, prefix_cache, lengths)
+        if padded:
+            if prefix_cache is not None:
                 raise NotImplementedError("generate(prefix_cache=...) with a padded batch: a prefix serves equal-length prompts only")
             # Ragged prompts (round 5).  The device KV cache holds equal-length rows (one position counter, RoPE by row index), and the reference itself only
             # ever sends one prompt x beams (conversation.py:231-243) — so a padded batch is served by LENGTH GROUPS: HF derives position_ids from the mask
             # (positions count real tokens only), i.e. every row generates exactly as its unpadded prompt would alone; rows of equal length share one
             # batched call, the results are re-assembled in row order, padded with pad_token_id like HF's finished rows.  Greedy and beam search are
             # deterministic: identical to per-row generation; sampling draws per group, not per batch (a different but equally valid stream).
-            m = hip.host_mask(attention_mask).to(torch.bool)
-            lens = m.sum(dim=1).tolist()
-            if len(set(lens)) > 1 or not bool(m.all()):
-                left = [bool(m[b, -1]) and not bool(m[b, 0]) for b in range(m.shape[0])]      # left-padded rows keep their LAST tokens
-                groups = {}
-                for b, n in enumerate(lens):
-                    groups.setdefault(n, []).append(b)
-                outs = [None] * m.shape[0]
-                for n, rows in sorted(groups.items()):
-                    emb = torch.stack([inputs_embeds[b, m.shape[1] - n:] if left[b] else inputs_embeds[b, :n] for b in rows], dim=0)
-                    ids = self.generate(inputs_embeds=emb, max_new_tokens=max_new_tokens, num_beams=num_beams, do_sample=do_sample, stopping_criteria=stopping_criteria,
-                                        use_cache=use_cache, min_length=min_length, top_p=top_p, repetition_penalty=repetition_penalty, length_penalty=length_penalty,
-                                        temperature=temperature, eos_token_id=eos_token_id, pad_token_id=pad_token_id, generator=generator, share_prefix=share_prefix, selection=selection, sync_every=sync_every)
-                    for j, b in enumerate(rows):
-                        outs[b] = ids[j]
-                width = max(o.shape[0] for o in outs)
-                res = torch.full((len(outs), width), pad_token_id, dtype=torch.long, device=outs[0].device)
-                for b, o in enumerate(outs):
-                    res[b, : o.shape[0]] = o
-                return res
-        return generation.generate(self, inputs_embeds, max_new_tokens=max_new_tokens, num_beams=num_beams, do_sample=do_sample,
-                                   min_length=min_length, top_p=top_p, temperature=temperature,
-                                   repetition_penalty=repetition_penalty, length_penalty=length_penalty,
-                                   stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
-                                   use_cache=use_cache, generator=generator, prefix=prefix_cache, stop_sequences=stop_sequences,
-                                   return_lengths=return_lengths, share_prefix=share_prefix, selection=selection, sync_every=sync_every)
+            groups = {}
+            for b, n in enumerate(lengths):
+                groups.setdefault(n, []).append(b)
+            outs, counts = [None] * B, [None] * B
+            for n, rows in sorted(groups.items()):
+                emb = torch.stack([inputs_embeds[b, spans[b][0]:spans[b][0] + n] for b in rows], dim=0)
+                out = generation._generate(self, emb, opts)
+                ids, cnt = out if return_lengths else (out, counts)
+                for j, b in enumerate(rows):
+                    outs[b], counts[b] = ids[j], cnt[j]
+            res = torch.full((B, max(o.shape[0] for o in outs)), pad_token_id, dtype=torch.long, device=outs[0].device)
+            for b, o in enumerate(outs):
+                res[b, : o.shape[0]] = o
+            return (res, counts) if return_lengths else res
+        return generation._generate(self, inputs_embeds, opts, prefix_cache)
 
     @classmethod
     def get_state_dict(cls, path, prefix="pytorch_model"):

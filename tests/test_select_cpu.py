@@ -171,7 +171,7 @@ def test_reference_merged_candidates_match_todays_topk(nb):
     eos = int(lg[0].argmax())
     beam_scores = torch.tensor([0.0, -0.3, -1.1, -2.0, -1e9][:nb - 1] + [-1e9] + [0.0] + [-1e9] * (nb - 1))
     with CB._patched({"beam_candidates": R.beam_candidates}):
-        cs, ct, cb = G._device_candidates(lg, prev[:, :300].long(), beam_scores, B, nb, 1.5, True, eos)
+        cs, ct, cb = G._device_candidates(lg, prev[:, :300].long(), beam_scores, B, nb, repetition_penalty=1.5, suppress_eos=True, eos_token_id=eos)
     logp = G._process_logits(lg.contiguous().log_softmax(dim=-1), prev[:, :300].long(), 0, 1.5, 1, eos)
     want_s, want_t = torch.topk((logp + beam_scores[:, None]).view(B, nb * V), 2 * nb, dim=1)
     live = want_s > -1e8                                           # behind a -1e9 beam score every candidate is the same fp32 number: any of them will do
