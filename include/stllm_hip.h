@@ -559,6 +559,47 @@ int stllm_attention_offset(int dtype, const void* q, int64_t q_bs, int64_t q_rs,
                            const int32_t* kv_len, int q_off, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
+ * stllm_attention_offset with a query offset and a length PER BATCH ROW (additive to ABI 7; always causal): a block of up to Sq new query rows per batch
+ * row, each batch row behind its own number of cached positions (LlamaModel.extend on a ragged cache).  q_off, kv_len: int32 [B] in device memory.  Batch
+ * row b holds q_off[b] cached positions and n_b = kv_len[b] - q_off[b] new ones; max_kv is the host-known upper bound of kv_len.  The kernels clamp
+ * kv_len[b] to [0, max_kv], q_off[b] to [0, kv_len[b]] and n_b to [0, Sq].  Query row i < n_b of row b sits at position q_off[b] + i and sees key j iff
+ * j <= q_off[b] + i.  Operand addressing and stride rules are those of stllm_attention_offset (q typically from a dense [B * Sq, 3 * hidden] scratch, K / V
+ * from the cache's own rows).
+ *   bf16 / fp16 at head_dim 128: the register-staged tile kernel or the key-split pair of stllm_attention_offset — the plan (key ranges, waves per workgroup,
+ *     grid) is the same pure function, evaluated at (B, H, Sq, max_kv); which of the two runs follows a rule measured on ragged rows (up to 512 (batch, head,
+ *     query tile) triples and at least 160 keys: the pair), "attn_ksplit" forces it as it does there and stllm_last_kernel() names what ran.  A key range
+ *     that begins behind a row's visible end leaves the empty record the merge weighs with 0.
+ *   fp32 at head_dim 128, max_kv <= 2048: the one-wave-per-row vector kernel.
+ *   anything else returns STLLM_ERR_UNSUPPORTED (stllm_last_error() says what): nothing else runs in its place.
+ * With q_off[b] = P and kv_len[b] = P + Sq for every b the output is bit-identical to stllm_attention_offset(q_off = P, Skv = P + Sq, kv_len = NULL) under
+ * the same FORCED "attn_ksplit" setting (0 / 1; 16-bit) — left to the rule (-1), the two entries follow rules of their own and may choose different
+ * schedules; the same call twice gives the same bits (fixed merge order).
+ * workspace: NULL (tile kernel only) or >= stllm_attention_offset_ragged_workspace_bytes(B, H, Sq, max_kv) bytes, 16-byte aligned, no initialisation needed.
+ * Memory regions.  Never read: K / V rows at or behind kv_len[b] of batch row b (uninitialised cache memory: the tile kernel runs with LIVE loads, zeros in
+ * the LDS instead of a load, not only masked scores); K / V of a row with n_b = 0 altogether.  Read, weightless: nothing.  Pad query rows (i >= n_b) may be
+ * read, whatever they hold (NaN included), and influence no other row.  Written: every out row (b, i < Sq) at columns [0, H * 128) — pad rows as exact zeros,
+ * never NaN; nothing else.  Workspace: every record the merge reads was written by the partial pass of the same call.
+ */
+int64_t stllm_attention_offset_ragged_workspace_bytes(int B, int H, int Sq, int max_kv);
+int stllm_attention_offset_ragged(int dtype, const void* q, int64_t q_bs, int64_t q_rs,
+                                  const void* k, int64_t k_bs, int64_t k_rs,
+                                  const void* v, int64_t v_bs, int64_t v_rs,
+                                  void* out, int64_t o_bs, int64_t o_rs,
+                                  int B, int H, int Sq, int max_kv, int D, float scale,
+                                  const int32_t* q_off, const int32_t* kv_len, void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
+ * Ragged KV-cache append of token BLOCKS (additive to ABI 7): stllm_kv_append_rows for S dense rows per batch row.  For every b and every
+ * i < min(n[b], S) with 0 <= pos0[b] + i < max_len the [k | v] columns of the dense fused row src[(b*S + i)*ld_src .. + 3*hidden) are copied to
+ * cache[b*batch_stride + (pos0[b] + i)*row_stride + the same columns].  pos0, n: int32 [B] in device memory.  Dtypes, strides and alignment as for
+ * stllm_kv_append_rows; B * S <= 65535.
+ * Memory regions.  Never read: the q columns of src, the pad rows i >= n[b], every row of a batch row with n[b] <= 0.  Never written: the q columns of the
+ * cache, any cache row other than (b, pos0[b] + i) for i < n[b], anything at all for a batch row with n[b] <= 0 or behind max_len.
+ */
+int stllm_kv_append_spans(int dtype, const void* src, int64_t ld_src, void* cache, int64_t batch_stride, int64_t row_stride,
+                          const int32_t* pos0, const int32_t* n, int B, int S, int hidden, int max_len, void* stream);
+
+/*
  * Row gather (token-block assembly, dynamic masking, residual-index selection, embedding lookup):
  *   dst[i, :] = scale * ((idx_a[i] >= 0 ? src_a[idx_a[i], :] : src_b[-idx_a[i]-1, :]) + (add ? add[idx_add[i], :] : 0))
  * all f32, D % 4 == 0.  The same kernel re-orders tokens between the BT-Adapter's spatial '(b t) p' and temporal

@@ -30,6 +30,15 @@ class VideoPrefix:
         self.cache, self.n_tokens = cache, n_tokens
 
 
+class Dialogue:
+    """N conversations in one ragged KV cache, between turns (Chat.answer_many(keep=True), Chat.follow_up).  cache: row b holds the K / V of everything row b
+    has seen and said so far except its last generated id, pending[b], which the next turn feeds first (generation.Continuation).  The dialogue lives on
+    TOKEN IDS: a follow-up sees exactly the ids the model generated."""
+
+    def __init__(self, cache, pending):
+        self.cache, self.pending, self.turns = cache, pending, 1
+
+
 class Chat:
     def __init__(self, model, device="cuda:0"):
         self.device = device
@@ -132,25 +141,65 @@ class Chat:
 
     def answer_many(self, img_list, questions_ids, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9,
                     repetition_penalty=1.0, length_penalty=1, temperature=1.0, max_length=2000, do_sample=False,
-                    stop_sequences=None, instruction=False, prefix=None, share_prefix=False, **kw):
+                    stop_sequences=None, instruction=False, prefix=None, share_prefix=False, keep=False, **kw):
         """N questions about ONE video in one ragged batch (generate(batching="ragged")): answer()'s truncation rule and its repetition_penalty = 1.5
         override per question, Chat's stop tokens as per-row stop_sequences (a row that ends in '###' is finished, the others go on).  prefix: a
         prefill_video(img_list) result — the video is prefilled once, forked to the N rows, and only [BOS] + question runs per row.  Returns one
         (text, ids) pair per question, each what answer() returns for that question alone.  share_prefix: the N rows (and their beams) read the prefilled video
-        where it is instead of a fork each (generate(share_prefix=True)).  **kw reaches generate(): selection="device", sync_every=K as in answer()."""
+        where it is instead of a fork each (generate(share_prefix=True)).  **kw reaches generate(): selection="device", sync_every=K as in answer().
+        keep: return (answers, Dialogue) — the rows' KV cache stays alive for follow_up() (num_beams == 1)."""
         if not instruction:
             repetition_penalty = 1.5
         embs, cache = self._prompts(img_list, questions_ids, max_length - max_new_tokens, prefix)
         if cache is not None:
             kw = dict(kw, prefix_cache=cache)
+        return self._ragged_round(embs, keep, kw, max_new_tokens=max_new_tokens, stop_sequences=stop_sequences, num_beams=num_beams, do_sample=do_sample,
+                                  min_length=min_length, top_p=top_p, repetition_penalty=repetition_penalty, length_penalty=length_penalty,
+                                  temperature=temperature, share_prefix=share_prefix)
+
+    def _ragged_round(self, embs, keep, kw, *, stop_sequences, **knobs):
+        """one generate(batching="ragged") over the right-padded prompts `embs`: (text, ids) per row, and with `keep` the Dialogue to go on from"""
         lens = torch.tensor([e.shape[0] for e in embs])
         batch = torch.nn.utils.rnn.pad_sequence(embs, batch_first=True)
         mask = (torch.arange(int(lens.max()))[None, :] < lens[:, None]).long()
         if stop_sequences is None:
             stop_sequences = self.stopping_criteria[0].stops
-        out, n_out = self.LLM.generate(inputs_embeds=batch, attention_mask=mask, max_new_tokens=max_new_tokens, stop_sequences=stop_sequences,
-                                       num_beams=num_beams, do_sample=do_sample, min_length=min_length, top_p=top_p, batching="ragged",
-                                       repetition_penalty=repetition_penalty, length_penalty=length_penalty, temperature=temperature,
-                                       return_lengths=True, share_prefix=share_prefix, **kw)
+        out, n_out, *cont = self.LLM.generate(inputs_embeds=batch, attention_mask=mask, stop_sequences=stop_sequences, batching="ragged",
+                                              return_lengths=True, return_cache=keep, **knobs, **kw)
         hip.gemm_workspace_check(batch.device, wait=True) if batch.is_cuda else None
-        return [self._decoded(row[:n]) for row, n in zip(out, n_out)]
+        answers = [self._decoded(row[:n]) for row, n in zip(out, n_out)]
+        return (answers, Dialogue(*cont[0])) if keep else answers
+
+    def turn_ids(self, question, closed=True):
+        """the ids of a follow-up turn: "Human: " + question + " ###Assistant: " behind a row that ended on '###' (closed), "###Human: ..." behind one
+        that ended on EOS or ran out of tokens"""
+        text = ("" if closed else "###") + "Human: " + question + " ###Assistant: "
+        return self.model.llama_tokenizer.encode_ids(text, add_special_tokens=False)
+
+    def follow_up(self, dialogue, turns_ids, max_new_tokens=300, num_beams=1, min_length=1, top_p=0.9, repetition_penalty=1.0, length_penalty=1, temperature=1.0,
+                  do_sample=False, stop_sequences=None, instruction=False, **kw):
+        """The next turn of every row of a Dialogue, in ONE ragged batch: row b's prompt is pending[b] + turns_ids[b] (turn_ids()), appended behind the
+        row's own cached positions (generate(prefix_cache=dialogue.cache, batching="ragged"): LlamaModel.extend on a ragged cache) — neither the video nor
+        the history is prefilled again.  Returns what answer_many returns and updates the dialogue.  The knobs are answer_many's (beams raise: generate(return_cache=True)).
+        The dialogue lives on TOKEN IDS: the follow-up sees exactly the ids the model generated.  The reference re-tokenises the decoded text of the whole
+        conversation on every turn (conversation.py:301-320), which need not give the same ids; what this equals is a from-scratch prefill of the
+        concatenated id sequence [video, turn 1, answer 1, turn 2, ...] of every row.
+        A turn that does not fit the cache gets a larger one (the working cache of every turn is a fork); past the model's position limit it is a ValueError."""
+        from .models.llama import cfg_max_len
+        if not instruction:
+            repetition_penalty = 1.5
+        cache = dialogue.cache
+        assert len(turns_ids) == cache.batch
+        ids = [[int(p)] + list(t) for p, t in zip(dialogue.pending.tolist(), turns_ids)]
+        have = cache.lens if cache.lens is not None else [cache.len] * cache.batch
+        limit = cfg_max_len(self.LLM.model.config)
+        need = max(h + len(i) for h, i in zip(have, ids)) + max_new_tokens
+        if need > limit:
+            raise ValueError(f"Chat.follow_up: the next turn needs {need} positions (history + turn + max_new_tokens), past the model's limit of {limit} "
+                             "(max_position_embeddings)")
+        embs = [self.model.embed_tokens(torch.tensor([i]))[0] for i in ids]
+        answers, nxt = self._ragged_round(embs, True, dict(kw, prefix_cache=cache), max_new_tokens=max_new_tokens, stop_sequences=stop_sequences,
+                                          num_beams=num_beams, do_sample=do_sample, min_length=min_length, top_p=top_p, repetition_penalty=repetition_penalty,
+                                          length_penalty=length_penalty, temperature=temperature)
+        dialogue.cache, dialogue.pending, dialogue.turns = nxt.cache, nxt.pending, dialogue.turns + 1
+        return answers

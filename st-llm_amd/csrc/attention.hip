@@ -38,6 +38,28 @@ struct AttnParams {
   float* ws; int nsplit, kps;           // attn_mfma_kernel<.., SPLIT>: partial records, key ranges per query chunk, keys per range (a multiple of 32)
 };
 
+// stllm_attention_offset_ragged: the RAGGED instantiations take the query offset PER BATCH ROW on top (with kv_len: row b holds q_off_tab[b] cached positions
+// and kv_len[b] - q_off_tab[b] new ones).  A type of its own, so that the kernel arguments of every other instantiation stay what they were.
+struct AttnRaggedParams : AttnParams { const int32_t* q_off_tab; };
+template <bool RAGGED> struct AttnParamsOf { using type = AttnParams; };
+template <> struct AttnParamsOf<true> { using type = AttnRaggedParams; };
+
+// the per-row tables of the RAGGED instantiations, clamped: 0 <= q_off <= kvlen <= Skv and n = kvlen - q_off <= Sq new rows.  A row without new positions
+// (n == 0) gets kvlen = 0: its workgroups walk no key and load nothing.  b is workgroup-uniform, so all three live in scalar registers.
+struct RaggedRow { int q_off, kvlen, n; };
+__device__ __forceinline__ RaggedRow ragged_row(const AttnRaggedParams& p, int b) {
+  RaggedRow r;
+  const int len = max(min(p.kv_len[b], p.Skv), 0);
+  r.q_off = max(min(p.q_off_tab[b], len), 0);
+  r.n = min(len - r.q_off, p.Sq);
+  r.kvlen = r.n > 0 ? r.q_off + r.n : 0;
+  return r;
+}
+// ... and what every other instantiation has always used, in the same shape
+__device__ __forceinline__ RaggedRow ragged_row(const AttnParams& p, int b) {
+  return RaggedRow{p.q_off, p.kv_len ? min(p.kv_len[b], p.Skv) : p.Skv, p.Sq};
+}
+
 constexpr float kNeg = -1.0e30f;
 
 // in-kernel timeline (tools/attn_trace.sh builds st-llm_amd/attn_trace/libstllm_hip.so with -DSTLLM_ATTN_TRACE; never in the shipped library):
@@ -73,8 +95,8 @@ constexpr int kSplRec = 132;   // floats per partial record: O[128], m (raw-scor
 // LIVE (the suffix pass of stllm_attention_shared only): key rows at or behind the batch row's kv_len are not LOADED (zeros instead) — the rows behind a
 // suffix's length are uninitialised memory, and a masked score of 0 times a NaN in V would reach the output.  Every other instantiation has LIVE = false
 // and compiles to what it always was.
-template <typename T, int DP, int NW, bool SPLIT = false, bool LIVE = false>
-__global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) {
+template <typename T, int DP, int NW, bool SPLIT = false, bool LIVE = false, bool RAGGED = false>
+__global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const typename AttnParamsOf<RAGGED>::type p) {
   constexpr int KS = DP / 16;          // k-steps of the S^T MFMA chain
   constexpr int DB = DP / 32;          // 32-row blocks of O^T
   constexpr int KPITCH = DP * 2 + 16;  // bytes per K row in LDS
@@ -94,7 +116,12 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
   const int q_blk0 = q_chunk * (32 * NW);
   const int qrow = q_blk0 + wave * 32 + li;  // this lane's query
   const int D = p.D;
-  const int kvlen = p.kv_len ? min(p.kv_len[b], p.Skv) : p.Skv;
+  static_assert(!RAGGED || LIVE, "the rows behind a ragged row's length are uninitialised: live loads only");
+  const RaggedRow rr = ragged_row(p, b);
+  const int kvlen = rr.kvlen;
+  // the query offset, read where it is used: per batch row (RAGGED) or the call's (every other instantiation, whose code this keeps what it was)
+#define ATTN_Q_OFF (RAGGED ? rr.q_off : p.q_off)
+  const int n_new = rr.n;       // the live query rows of this batch row (RAGGED; the rows behind them are pad and come out as zeros)
 
   // ---- Q fragments (B operand of S^T): lane holds Q[q][ks*16 + lh*8 .. +8] ------------------------
   i32x4 qf[KS];
@@ -116,9 +143,12 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
   float m_run = kNeg, l_run = 0.0f;
 
   int kv_end = kvlen;
-  if (p.causal) kv_end = min(kv_end, p.q_off + q_blk0 + 32 * NW);  // keys beyond the last query of the block are masked
+  if (p.causal) kv_end = min(kv_end, ATTN_Q_OFF + q_blk0 + 32 * NW);  // keys beyond the last query of the block are masked
   const int kv_begin = SPLIT ? k_range * p.kps : 0;
   if (SPLIT) kv_end = min(kv_end, kv_begin + p.kps);
+  if constexpr (RAGGED) {
+    if (q_blk0 >= n_new) kv_end = 0;   // every query row of this workgroup is pad: it walks no key, loads nothing and stores its zeros / empty records
+  }
   const char* kbase = p.k + ((int64_t)b * p.k_bs + (int64_t)h * D) * 2;
   const char* vbase = p.v + ((int64_t)b * p.v_bs + (int64_t)h * D) * 2;
 
@@ -137,7 +167,7 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
       vreg[c] = ok ? *reinterpret_cast<const i32x4*>(vbase + ((int64_t)kv * p.v_rs + cc * 8) * 2) : z;
     }
   };
-  const int wave_q_last = p.q_off + q_blk0 + wave * 32 + 31;  // position of the last query row of this wave (causal tile skipping)
+  const int wave_q_last = ATTN_Q_OFF + q_blk0 + wave * 32 + 31;  // position of the last query row of this wave (causal tile skipping)
   if (kv_end > kv_begin) load_tile(kv_begin);
   for (int kv0 = kv_begin; kv0 < kv_end; kv0 += 32) {
     __syncthreads();  // previous tile fully consumed
@@ -158,6 +188,11 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
     __syncthreads();
     if (kv0 + 32 < kv_end) load_tile(kv0 + 32);
     if (p.causal && kv0 > wave_q_last) continue;  // every key of this tile is in the future of every query of this wave
+    if constexpr (RAGGED) {
+      // a wave whose 32 query rows are all pad took part in the loads and the barriers and skips the MFMA / softmax work: its rows come out as zeros
+      // (tile kernel) or as empty records (key split) whatever its state holds (wave-uniform, like the test above)
+      if (q_blk0 + wave * 32 >= n_new) continue;
+    }
 
     // ---- S^T = K . Q^T ------------------------------------------------------------------------------
     f32x16 s;
@@ -169,12 +204,12 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
       s = Elem<T>::mfma(kf, qf[ks], s);
     }
     // ---- mask + online softmax (per-lane query); scores stay RAW, the scale is folded into the exp2 argument ----
-    const bool need_mask = (kv0 + 32 > kvlen) || (p.causal && kv0 + 31 > p.q_off + q_blk0 + wave * 32);  // wave-uniform
+    const bool need_mask = (kv0 + 32 > kvlen) || (p.causal && kv0 + 31 > ATTN_Q_OFF + q_blk0 + wave * 32);  // wave-uniform
     if (need_mask) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int kv = kv0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const bool dead = (kv >= kvlen) || (p.causal && kv > qrow + p.q_off);
+        const bool dead = (kv >= kvlen) || (p.causal && kv > qrow + ATTN_Q_OFF);
         s[r] = dead ? kNeg : s[r];
       }
     }
@@ -227,7 +262,8 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
     if (qrow < p.Sq) {
       // a row that saw no key of this range (its tiles skipped, or every key of them masked) has m_run == kNeg and, where a tile was walked for the
       // sake of the wave's other rows, exp2(0) weights in l / O: its record is the empty state, which the merge weighs with exactly 0
-      const bool empty = m_run <= 0.5f * kNeg;
+      bool empty = m_run <= 0.5f * kNeg;
+      if constexpr (RAGGED) empty = empty || qrow >= n_new;   // a pad row's record is empty too (the merge writes its zeros)
       float* rec = p.ws + ((((int64_t)b * p.H + h) * p.Sq + qrow) * p.nsplit + k_range) * kSplRec;
 #pragma unroll
       for (int i = 0; i < DB; ++i)
@@ -253,12 +289,16 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const AttnParams p) 
           uint2 pk;
           pk.x = Elem<T>::pack2(o[i][4 * g + 0] * inv, o[i][4 * g + 1] * inv);
           pk.y = Elem<T>::pack2(o[i][4 * g + 2] * inv, o[i][4 * g + 3] * inv);
+          if constexpr (RAGGED) {
+            if (qrow >= n_new) { pk.x = 0u; pk.y = 0u; }   // pad rows are written as exact zeros (their state may hold anything, NaN included)
+          }
           *reinterpret_cast<uint2*>(op + d0) = pk;
         }
       }
     }
   }
 }
+#undef ATTN_Q_OFF
 
 // ---- resident-K/V variant for short key sequences (ViT: 257 keys, Q-Former cross-attention) ----------------
 // The whole K (row-major, padded rows) and V^T of one (batch, head) are staged into LDS ONCE (<= 116 KiB for 288 keys x
@@ -1026,7 +1066,9 @@ int launch_dma(const AttnParams& p, hipStream_t stream, int nw_req) {
 // ---- exact fp32 path: one wave per query row -----------------------------------------------------
 constexpr int kF32MaxKv = 2048;
 
-__global__ __launch_bounds__(256) void attn_f32_kernel(const AttnParams p) {
+// RAGGED (attn_f32_ragged_kernel, stllm_attention_offset_ragged): offset and length per batch row; a pad row is written as zeros and reads no key.
+template <bool RAGGED>
+__device__ __forceinline__ void attn_f32_body(const typename AttnParamsOf<RAGGED>::type& p) {
   __shared__ float q_s[4][128];
   __shared__ float sc[4][kF32MaxKv];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1034,8 +1076,16 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnParams p) {
   const int qrow = blockIdx.x * 4 + w;
   if (qrow >= p.Sq) return;  // no block-level sync below
   const int D = p.D;
-  const int kvlen = p.kv_len ? min(p.kv_len[b], p.Skv) : p.Skv;
-  const int kv_end = p.causal ? min(kvlen, p.q_off + qrow + 1) : kvlen;
+  const RaggedRow rr = ragged_row(p, b);
+  const int kvlen = rr.kvlen;
+  if constexpr (RAGGED) {
+    if (qrow >= rr.n) {
+      float* o = reinterpret_cast<float*>(p.o) + (int64_t)b * p.o_bs + (int64_t)qrow * p.o_rs + (int64_t)h * p.D;
+      for (int d = lane; d < p.D; d += 64) o[d] = 0.0f;
+      return;
+    }
+  }
+  const int kv_end = p.causal ? min(kvlen, (RAGGED ? rr.q_off : p.q_off) + qrow + 1) : kvlen;
   const float* q = reinterpret_cast<const float*>(p.q) + (int64_t)b * p.q_bs + (int64_t)qrow * p.q_rs + (int64_t)h * D;
   const float* kb = reinterpret_cast<const float*>(p.k) + (int64_t)b * p.k_bs + (int64_t)h * D;
   const float* vb = reinterpret_cast<const float*>(p.v) + (int64_t)b * p.v_bs + (int64_t)h * D;
@@ -1073,6 +1123,9 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnParams p) {
     o[d] = acc * inv;
   }
 }
+
+__global__ __launch_bounds__(256) void attn_f32_kernel(const AttnParams p) { attn_f32_body<false>(p); }
+__global__ __launch_bounds__(256) void attn_f32_ragged_kernel(const AttnRaggedParams p) { attn_f32_body<true>(p); }
 
 // ---- exact fp32 path on the MATRIX cores (round 4): v_mfma_f32_32x32x2_f32, bit-equal to an fmaf chain per output --------------------
 // The one-wave-per-row kernel above re-reads the whole K and V of a head from L2 for every query row (181 KB per ViT row: ~12 GB per
@@ -1632,9 +1685,16 @@ extern "C" int stllm_attention(int dtype, const void* q, int64_t q_bs, int64_t q
 // =====================================================================================================
 namespace {
 
-template <typename T>
-__global__ __launch_bounds__(64) void attn_ksplit_merge_kernel(const AttnParams p) {
+// RAGGED: a pad query row (every record of it is empty: 1 / ll would be infinite) is written as zeros.
+template <typename T, bool RAGGED = false>
+__global__ __launch_bounds__(64) void attn_ksplit_merge_kernel(const typename AttnParamsOf<RAGGED>::type p) {
   const int lane = threadIdx.x, qrow = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  if constexpr (RAGGED) {
+    if (qrow >= ragged_row(p, b).n) {
+      *reinterpret_cast<uint32_t*>(p.o + ((int64_t)b * p.o_bs + (int64_t)qrow * p.o_rs + (int64_t)h * 128 + 2 * lane) * 2) = 0u;
+      return;
+    }
+  }
   const float* rec = p.ws + (((int64_t)b * p.H + h) * p.Sq + qrow) * p.nsplit * kSplRec;
   float mm = kNeg;
   for (int s = 0; s < p.nsplit; ++s) mm = fmaxf(mm, rec[s * kSplRec + 128]);
@@ -1670,24 +1730,24 @@ KsplitPlan ksplit_plan(int B, int H, int Sq, int Skv) {
   return pl;
 }
 
-template <typename T, int NW>
-void launch_ksplit_nw(const AttnParams& p, const KsplitPlan& pl, hipStream_t stream) {
-  hipLaunchKernelGGL((attn_mfma_kernel<T, 128, NW, true>), dim3(pl.chunks * pl.nsplit, p.H, p.B), dim3(64 * NW), 0, stream, p);
+template <typename T, int NW, bool RAGGED>
+void launch_ksplit_nw(const typename AttnParamsOf<RAGGED>::type& p, const KsplitPlan& pl, hipStream_t stream) {
+  hipLaunchKernelGGL((attn_mfma_kernel<T, 128, NW, true, RAGGED, RAGGED>), dim3(pl.chunks * pl.nsplit, p.H, p.B), dim3(64 * NW), 0, stream, p);
 }
 
-template <typename T>
-int launch_ksplit(AttnParams p, hipStream_t stream) {
+template <typename T, bool RAGGED = false>
+int launch_ksplit(typename AttnParamsOf<RAGGED>::type p, hipStream_t stream) {
   const KsplitPlan pl = ksplit_plan(p.B, p.H, p.Sq, p.Skv);
   p.nsplit = pl.nsplit;
   p.kps = pl.kps;
   switch (pl.nw) {
-    case 1: launch_ksplit_nw<T, 1>(p, pl, stream); break;
-    case 2: launch_ksplit_nw<T, 2>(p, pl, stream); break;
-    case 3: launch_ksplit_nw<T, 3>(p, pl, stream); break;
-    default: launch_ksplit_nw<T, 4>(p, pl, stream); break;
+    case 1: launch_ksplit_nw<T, 1, RAGGED>(p, pl, stream); break;
+    case 2: launch_ksplit_nw<T, 2, RAGGED>(p, pl, stream); break;
+    case 3: launch_ksplit_nw<T, 3, RAGGED>(p, pl, stream); break;
+    default: launch_ksplit_nw<T, 4, RAGGED>(p, pl, stream); break;
   }
-  hipLaunchKernelGGL(attn_ksplit_merge_kernel<T>, dim3(p.Sq, p.H, p.B), dim3(64), 0, stream, p);
-  STLLM_CHECK_LAUNCH("stllm_attention_offset(key split)");
+  hipLaunchKernelGGL((attn_ksplit_merge_kernel<T, RAGGED>), dim3(p.Sq, p.H, p.B), dim3(64), 0, stream, p);
+  STLLM_CHECK_LAUNCH(RAGGED ? "stllm_attention_offset_ragged(key split)" : "stllm_attention_offset(key split)");
   stllm_set_last_kernel("attn_ksplit_kernel");
   return STLLM_OK;
 }
@@ -1712,6 +1772,34 @@ int dispatch_offset(const AttnParams& p, hipStream_t stream) {
   if (p.D == 128) return nw == 1 ? launch_mfma<T, 128, 1>(p, stream) : nw == 2 ? launch_mfma<T, 128, 2>(p, stream) : launch_mfma<T, 128, 3>(p, stream);
   if (p.D == 88) return nw == 1 ? launch_mfma<T, 96, 1>(p, stream) : launch_mfma<T, 96, 3>(p, stream);
   return nw == 1 ? launch_mfma<T, 64, 1>(p, stream) : launch_mfma<T, 64, 2>(p, stream);
+}
+
+template <typename T, int NW>
+int launch_mfma_ragged(const AttnRaggedParams& p, hipStream_t stream) {
+  dim3 grid((p.Sq + 32 * NW - 1) / (32 * NW), p.H, p.B), block(64 * NW);
+  hipLaunchKernelGGL((attn_mfma_kernel<T, 128, NW, false, true, true>), grid, block, 0, stream, p);
+  STLLM_CHECK_LAUNCH("stllm_attention_offset_ragged");
+  return STLLM_OK;
+}
+
+// stllm_attention_offset_ragged, 16-bit at head_dim 128: dispatch_offset's two schedules — the same plan and the same waves per workgroup at (B, H, Sq, max_kv) —
+// on the RAGGED instantiations.  The rule is the region measured on ragged rows (tools/attn_bench.py --ragged-suffix, MI355X, bf16, 32 heads, graph replays,
+// us tile -> key split; profiles/ragged_extend.md): B = 4, prefixes 300 - 610, n = 8: 47 -> 22; prefixes 560 - 1100, n = 8 - 40: 77 -> 33; prefixes 330 - 1024 with
+// one row at n = 0: 70 -> 30; prefixes 580 - 620, n = 20: 50 -> 24; B = 8, prefixes 300 - 1100, n = 8: 80 -> 52, n = 8 - 40 (two query tiles, 512 triples): 78 -> 50.
+// It won on every shape measured, so: up to 512 (batch, head, query tile) triples — ksplit_wins stops at 320, where its own measurements end — and at least 160
+// keys (below ~ 600 keys the bound is ksplit_wins', measured on uniform rows only).  Larger problems were not measured: they stay on the tile kernel.
+bool ksplit_wins_ragged(const AttnParams& p) {
+  const int q_tiles = (p.Sq + 31) / 32;
+  return (int64_t)p.B * p.H * q_tiles <= 512 && p.Skv >= 160;
+}
+
+template <typename T>
+int dispatch_offset_ragged(const AttnRaggedParams& p, hipStream_t stream) {
+  const int opt = stllm_options().attn_ksplit;
+  if (p.ws && opt != 0 && (opt > 0 || ksplit_wins_ragged(p))) return launch_ksplit<T, true>(p, stream);
+  stllm_set_last_kernel("attn_mfma_kernel");
+  const int nw = p.Sq <= 32 ? 1 : (p.Sq <= 64 ? 2 : 3);
+  return nw == 1 ? launch_mfma_ragged<T, 1>(p, stream) : nw == 2 ? launch_mfma_ragged<T, 2>(p, stream) : launch_mfma_ragged<T, 3>(p, stream);
 }
 
 }  // namespace
@@ -1758,6 +1846,50 @@ extern "C" int stllm_attention_offset(int dtype, const void* q, int64_t q_bs, in
   }
   stllm_set_error("stllm_attention_offset: bad dtype %d", dtype);
   return STLLM_ERR_BAD_DTYPE;
+}
+
+extern "C" int64_t stllm_attention_offset_ragged_workspace_bytes(int B, int H, int Sq, int max_kv) {
+  return stllm_attention_offset_workspace_bytes(B, H, Sq, max_kv);
+}
+
+// stllm_attention_offset with a query offset and a length PER BATCH ROW (always causal): row b holds q_off[b] cached positions and kv_len[b] - q_off[b]
+// (0 .. Sq) new ones.  Schedule, plan and grid come from (B, H, Sq, max_kv) exactly as stllm_attention_offset derives them from Skv; the per-row bounds
+// live in the kernels (attn_mfma_kernel<.., LIVE, RAGGED>, attn_ksplit_merge_kernel<T, RAGGED>, attn_f32_ragged_kernel).
+extern "C" int stllm_attention_offset_ragged(int dtype, const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs,
+                                             int64_t k_rs, const void* v, int64_t v_bs, int64_t v_rs, void* out, int64_t o_bs,
+                                             int64_t o_rs, int B, int H, int Sq, int max_kv, int D, float scale, const int32_t* q_off,
+                                             const int32_t* kv_len, void* workspace, int64_t workspace_bytes, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  STLLM_CHECK_ARG(q && k && v && out && q_off && kv_len, "stllm_attention_offset_ragged: null pointer");
+  STLLM_CHECK_ARG(B > 0 && H > 0 && Sq > 0 && max_kv > 0, "stllm_attention_offset_ragged: empty problem");
+  if (D != 128 || (dtype != STLLM_BF16 && dtype != STLLM_F16 && dtype != STLLM_F32)) {
+    stllm_set_error("stllm_attention_offset_ragged: head_dim %d / dtype %d unsupported (bf16 / fp16 / fp32 at head_dim 128)", D, dtype);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  if (dtype == STLLM_F32 && max_kv > kF32MaxKv) {
+    stllm_set_error("stllm_attention_offset_ragged: fp32 with max_kv %d > %d unsupported (the vector kernel keeps a row's scores in the LDS)", max_kv, kF32MaxKv);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  STLLM_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out), "stllm_attention_offset_ragged: pointers must be 16-byte aligned");
+  STLLM_CHECK_ARG(q_rs % 8 == 0 && k_rs % 8 == 0 && v_rs % 8 == 0 && o_rs % 8 == 0 && q_bs % 8 == 0 && k_bs % 8 == 0 &&
+                      v_bs % 8 == 0 && o_bs % 8 == 0, "stllm_attention_offset_ragged: strides must be multiples of 8 elements");
+  STLLM_CHECK_ARG(((reinterpret_cast<uintptr_t>(q_off) | reinterpret_cast<uintptr_t>(kv_len)) & 3) == 0, "stllm_attention_offset_ragged: tables must be 4-byte aligned");
+  AttnRaggedParams p{};
+  p.q = (const char*)q; p.q_bs = q_bs; p.q_rs = q_rs;
+  p.k = (const char*)k; p.k_bs = k_bs; p.k_rs = k_rs;
+  p.v = (const char*)v; p.v_bs = v_bs; p.v_rs = v_rs;
+  p.o = (char*)out; p.o_bs = o_bs; p.o_rs = o_rs;
+  p.B = B; p.H = H; p.Sq = Sq; p.Skv = max_kv; p.D = D;
+  p.scale = scale; p.scale_log2 = scale * 1.44269504088896340736f;
+  p.causal = 1; p.kv_len = kv_len; p.q_off_tab = q_off;
+  if (workspace && aligned16(workspace) && workspace_bytes >= stllm_attention_offset_ragged_workspace_bytes(B, H, Sq, max_kv)) p.ws = reinterpret_cast<float*>(workspace);
+  if (dtype == STLLM_F32) {
+    stllm_set_last_kernel("attn_f32_kernel");
+    hipLaunchKernelGGL(attn_f32_ragged_kernel, dim3((Sq + 3) / 4, H, B), dim3(256), 0, stream, p);
+    STLLM_CHECK_LAUNCH("stllm_attention_offset_ragged(fp32)");
+    return STLLM_OK;
+  }
+  return dtype == STLLM_BF16 ? dispatch_offset_ragged<bf16_t>(p, stream) : dispatch_offset_ragged<f16_t>(p, stream);
 }
 
 extern "C" int64_t stllm_attention_decode_workspace_bytes(int B, int H, int Skv) {

@@ -126,6 +126,19 @@ __global__ __launch_bounds__(256) void kv_append_rows_kernel(const char* __restr
   reinterpret_cast<uint4*>(cache + (int64_t)b * batch_stride + (int64_t)ps * row_stride + col0_bytes)[c] = v;
 }
 
+// ragged KV-cache append of token BLOCKS (stllm_kv_append_spans): the [k | v] bytes of dense row b * S + i -> the cache row of batch entry b at position
+// pos0[b] + i, for i < min(n[b], S); 16 bytes per lane, blockIdx.y = b * S + i.  Pad rows (i >= n[b]) and positions outside [0, max_len) write nothing.
+__global__ __launch_bounds__(256) void kv_append_spans_kernel(const char* __restrict__ src, int64_t src_stride, char* __restrict__ cache,
+                                                              int64_t batch_stride, int64_t row_stride, const int32_t* __restrict__ pos0,
+                                                              const int32_t* __restrict__ n, int S, int max_len, int col0_bytes, int n16) {
+  const int r = blockIdx.y, b = r / S, i = r - b * S, c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n16 || i >= n[b]) return;
+  const int64_t ps = (int64_t)pos0[b] + i;
+  if (ps < 0 || ps >= max_len) return;
+  const uint4 v = reinterpret_cast<const uint4*>(src + (int64_t)r * src_stride + col0_bytes)[c];
+  reinterpret_cast<uint4*>(cache + (int64_t)b * batch_stride + ps * row_stride + col0_bytes)[c] = v;
+}
+
 // ---- token selection: stllm_select_tokens / stllm_beam_candidates (include/stllm_hip.h) --------------------------------------------------------------
 // One workgroup per row; the row lives in the LDS as fp32 from the staging on (V <= ~40 k floats), every later pass reads the LDS.  Reductions: a
 // per-thread partial in index order, the xor butterfly inside a wave, the four wave results combined in a fixed order — no atomics, so a launch is
@@ -425,6 +438,30 @@ extern "C" int stllm_kv_append_rows(int dtype, const void* src, int64_t ld_src, 
   hipLaunchKernelGGL(kv_append_rows_kernel, dim3((n16 + 255) / 256, B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const char*>(src), ld_src * e, reinterpret_cast<char*>(cache), batch_stride * e, row_stride * e, pos, max_len, col0, n16);
   STLLM_CHECK_LAUNCH("stllm_kv_append_rows");
+  return STLLM_OK;
+}
+
+extern "C" int stllm_kv_append_spans(int dtype, const void* src, int64_t ld_src, void* cache, int64_t batch_stride, int64_t row_stride,
+                                     const int32_t* pos0, const int32_t* n, int B, int S, int hidden, int max_len, void* stream) {
+  STLLM_CHECK_ARG(src && cache && pos0 && n, "stllm_kv_append_spans: null pointer");
+  STLLM_CHECK_ARG(B > 0 && S > 0 && hidden > 0 && max_len > 0 && (int64_t)B * S <= 65535, "stllm_kv_append_spans: bad B=%d S=%d hidden=%d max_len=%d (B * S <= 65535)",
+                  B, S, hidden, max_len);
+  int e;
+  switch (dtype) {
+    case STLLM_BF16: case STLLM_F16: e = 2; break;
+    case STLLM_F32: e = 4; break;
+    default: stllm_set_error("stllm_kv_append_spans: bad dtype %d", dtype); return STLLM_ERR_BAD_DTYPE;
+  }
+  STLLM_CHECK_ARG(ld_src >= 3 * (int64_t)hidden && row_stride >= 3 * (int64_t)hidden && batch_stride >= (int64_t)max_len * row_stride,
+                  "stllm_kv_append_spans: rows of 3 * hidden elements, max_len rows per batch entry");
+  STLLM_CHECK_ARG(((int64_t)hidden * e) % 16 == 0 && (ld_src * e) % 16 == 0 && (row_stride * e) % 16 == 0 && (batch_stride * e) % 16 == 0 &&
+                      aligned16(src) && aligned16(cache) && (reinterpret_cast<uintptr_t>(pos0) & 3) == 0 && (reinterpret_cast<uintptr_t>(n) & 3) == 0,
+                  "stllm_kv_append_spans: 16-byte vector copies need 16-byte aligned pointers, strides and hidden");
+  const int col0 = hidden * e, n16 = (2 * hidden * e) / 16;
+  hipLaunchKernelGGL(kv_append_spans_kernel, dim3((n16 + 255) / 256, B * S), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const char*>(src), ld_src * e, reinterpret_cast<char*>(cache), batch_stride * e, row_stride * e, pos0, n, S, max_len, col0,
+                     n16);
+  STLLM_CHECK_LAUNCH("stllm_kv_append_spans");
   return STLLM_OK;
 }
 

@@ -101,8 +101,12 @@ def _ends_in_stop(ids, stop_sequences):
 # the sampling and stopping options of generate() (see its docstring) and their defaults, stated once: every public entry builds one Options from its keywords
 _DEFAULTS = dict(max_new_tokens=16, num_beams=1, do_sample=False, min_length=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0, length_penalty=1.0,
                  stopping_criteria=None, eos_token_id=2, pad_token_id=0, use_cache=True, generator=None, stop_sequences=None, return_lengths=False,
-                 share_prefix=False, selection="torch", sync_every=1)
+                 share_prefix=False, selection="torch", sync_every=1, return_cache=False)
 Options = collections.namedtuple("Options", list(_DEFAULTS), defaults=list(_DEFAULTS.values()))
+# generate(return_cache=True): what a later turn continues from.  cache: the working KV cache, truncated per row to the positions whose K / V certainly belong
+# to the row's own tokens — prompt_len_b + n_gen_b - 1 (a finished row was fed pads meanwhile: dropped); pending: LongTensor [B] on the CPU, every row's
+# last generated id, which has not been fed yet — the first token of the row's next prompt
+Continuation = collections.namedtuple("Continuation", "cache pending")
 
 
 class _CacheStepper:
@@ -110,7 +114,9 @@ class _CacheStepper:
 
     def __init__(self, lm_wrapper, inputs_embeds, opts, prefix=None, lengths=None):
         """prefix: a KVCache holding the prompts' first positions (a prefilled video; one row per prompt, or with `lengths` one row shared by all), left
-        as it was: the work happens on a fork (a copy per row) or, share_prefix, on a cache that reads it where it is (KVCache.share).
+        as it was: the work happens on a fork (a copy per row) or, share_prefix, on a cache that reads it where it is (KVCache.share).  A prefix whose rows
+        have different lengths (prefix.lens set: one row per prompt, the rows of an earlier ragged batch) is forked and extended by LlamaModel.extend's
+        ragged path; it cannot be shared.
         lengths: row b of the right-padded `inputs_embeds` holds lengths[b] tokens -> a ragged cache; the beams of a prompt inherit its length."""
         self.m, self.lm = lm_wrapper, lm_wrapper.model
         self.use_cache, self.rep = opts.use_cache, opts.num_beams      # rep: beams per prompt
@@ -130,6 +136,9 @@ class _CacheStepper:
                 raise NotImplementedError("generate(share_prefix=True, lengths=...) with beams needs prefix=: a ragged prompt cache cannot be a shared base")
         elif prefix is not None and (not self.use_cache or prefix.batch != B):
             raise ValueError("generate(prefix=...): needs use_cache and one prefix row per prompt")
+        if prefix is not None and prefix.lens is not None and (share or prefix.batch != B):
+            raise NotImplementedError("generate(prefix=<a cache whose rows have different lengths>): one prefix row per prompt, share_prefix off "
+                                      "(ragged rows cannot be a shared base)")
 
         def per_beam(t):                          # row b -> rows [b * rep, (b + 1) * rep)
             return t.repeat_interleave(self.rep, dim=0) if self.rep > 1 else t
@@ -189,7 +198,7 @@ class _CacheStepper:
 def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sample=False, min_length=0, top_p=1.0,
              temperature=1.0, repetition_penalty=1.0, length_penalty=1.0, stopping_criteria=None, eos_token_id=2,
              pad_token_id=0, use_cache=True, generator=None, prefix=None, lengths=None, stop_sequences=None, return_lengths=False,
-             share_prefix=False, selection="torch", sync_every=1):
+             share_prefix=False, selection="torch", sync_every=1, return_cache=False):
     """Returns the generated ids [B, n] (the prompt has no ids), HF semantics as described in the module docstring.
     prefix: a KVCache that already holds the first positions of every prompt (LlamaModel.prefill(cache=...) / Chat.prefill_video); `inputs_embeds` is then
     the remainder of the prompt, appended behind it in one pass (LlamaModel.extend).  The prefix is left unchanged.
@@ -208,11 +217,14 @@ def generate(lm_wrapper, inputs_embeds, max_new_tokens=16, num_beams=1, do_sampl
     ids DIFFER from those of torch.multinomial; the same seed reproduces them.  A vocabulary that does not fit the LDS raises.
     sync_every: "device", num_beams == 1 only — the host reads `unfinished` back every sync_every-th step instead of every step; finished rows emit
     pad_token_id meanwhile, and the result is cut where every row had finished: the same ids.  A `stopping_criteria` callable needs the ids of every
-    step and forces 1."""
+    step and forces 1.
+    return_cache: additionally return a Continuation(cache, pending) as the LAST element of the result (num_beams == 1, use_cache; both selections): the
+    working cache cut per row to its own tokens, and every row's last generated id, not fed yet.  A later generate(prefix=cont.cache, lengths=...) whose
+    row b starts with pending[b] continues row b (Chat.follow_up)."""
     opts = Options(max_new_tokens=max_new_tokens, num_beams=num_beams, do_sample=do_sample, min_length=min_length, top_p=top_p, temperature=temperature,
                    repetition_penalty=repetition_penalty, length_penalty=length_penalty, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
                    pad_token_id=pad_token_id, use_cache=use_cache, generator=generator, stop_sequences=stop_sequences, return_lengths=return_lengths,
-                   share_prefix=share_prefix, selection=selection, sync_every=sync_every)
+                   share_prefix=share_prefix, selection=selection, sync_every=sync_every, return_cache=return_cache)
     return _generate(lm_wrapper, inputs_embeds, opts, prefix, lengths)
 
 
@@ -222,19 +234,36 @@ def _generate(lm_wrapper, inputs_embeds, opts, prefix=None, lengths=None):
     if opts.selection not in ("torch", "device"):
         raise ValueError(f"generate(selection={opts.selection!r}): 'torch' or 'device'")
     opts = opts._replace(stop_sequences=list(opts.stop_sequences) if opts.stop_sequences else None)
+    if opts.return_cache and not opts.use_cache:
+        raise ValueError("generate(return_cache=True) needs use_cache: what is returned is the KV cache")
+    if opts.return_cache and opts.num_beams > 1:
+        raise NotImplementedError("generate(return_cache=True) with beams: the rows of the working cache are beams, not prompts (num_beams == 1 only)")
     if opts.num_beams > 1:
         return _generate_beams(lm_wrapper, inputs_embeds, opts, prefix, lengths)
     loop = _generate_device if opts.selection == "device" else _generate_torch
     return loop(lm_wrapper, inputs_embeds, opts, prefix, lengths)
 
 
-def _finish(ids, n_gen, opts):
+def _finish(ids, n_gen, opts, cont=None):
     """the common tail of the loops.  Every token was read back on the host, so the stream is idle: a timed-out split-K exchange anywhere in this
-    generate() call must not come back as plausible-looking ids.  n_gen: the number of generated tokens per row, returned on request."""
+    generate() call must not come back as plausible-looking ids.  n_gen: the number of generated tokens per row, returned on request.
+    cont: the Continuation of return_cache, appended to the result."""
     if ids.device.type == "cuda":
         from . import hip
         hip.gemm_workspace_check(ids.device, wait=True)
-    return (ids, n_gen) if opts.return_lengths else ids
+    out = (ids, n_gen) if opts.return_lengths else (ids,)
+    out = out + (cont,) if opts.return_cache else out
+    return out if len(out) > 1 else out[0]
+
+
+def _continuation(st, ids, n_gen, steps):
+    """return_cache: `steps` tokens were selected and steps - 1 of them fed, so row b holds its prompt plus steps - 1 positions, of which the first
+    n_gen[b] - 1 are its own tokens (the last one it generated is pending; what a finished row was fed afterwards is padding)"""
+    cache = st.cache
+    have = cache.lens if cache.lens is not None else [cache.len] * cache.batch
+    cache.truncate([h - steps + n for h, n in zip(have, n_gen)])
+    host = ids.cpu()
+    return Continuation(cache, torch.tensor([int(host[b, n - 1]) for b, n in enumerate(n_gen)], dtype=torch.long))
 
 
 def _generate_torch(lm_wrapper, inputs_embeds, o, prefix, lengths):
@@ -262,7 +291,8 @@ def _generate_torch(lm_wrapper, inputs_embeds, o, prefix, lengths):
         if unfinished.max() == 0 or _stop(o.stopping_criteria, ids, scores) or ids.shape[1] >= o.max_new_tokens:
             break
         st.advance(nxt)
-    return _finish(ids, n_gen.tolist() if o.return_lengths else None, o)
+    n_host = n_gen.tolist() if o.return_lengths or o.return_cache else None
+    return _finish(ids, n_host, o, _continuation(st, ids, n_host, ids.shape[1]) if o.return_cache else None)
 
 
 def _generate_beams(lm_wrapper, inputs_embeds, opts, prefix, lengths):
@@ -404,4 +434,4 @@ def _generate_device(lm_wrapper, inputs_embeds, opts, prefix, lengths):
         st.advance(nxt, on_device=True)
     n_host = n_gen.tolist()
     n = t if stopping_criteria is not None else max(n_host)      # sync_every > 1 runs past the step at which every row had finished: cut there
-    return _finish(ids[:, :n].long(), n_host, opts)
+    return _finish(ids[:, :n].long(), n_host, opts, _continuation(st, ids, n_host, t) if opts.return_cache else None)

@@ -29,7 +29,8 @@ EXPORTS = ["stllm_last_error", "stllm_abi_version", "stllm_last_kernel", "stllm_
            "stllm_lora_down_workspace_bytes", "stllm_lora_down", "stllm_llama_layers_lora_scratch_bytes", "stllm_llama_layers_lora",
            "stllm_attention_offset_workspace_bytes", "stllm_attention_offset", "stllm_llama_layers_extend", "stllm_gemv_w8", "stllm_gemv_q4",
            "stllm_attention_decode_ragged_workspace_bytes", "stllm_attention_decode_ragged", "stllm_kv_append_rows",
-           "stllm_attention_shared_workspace_bytes", "stllm_attention_shared", "stllm_select_tokens", "stllm_beam_candidates"]
+           "stllm_attention_shared_workspace_bytes", "stllm_attention_shared", "stllm_select_tokens", "stllm_beam_candidates",
+           "stllm_attention_offset_ragged_workspace_bytes", "stllm_attention_offset_ragged", "stllm_kv_append_spans"]
 
 
 def torch_dtype(d):
@@ -203,6 +204,9 @@ def _bind(L, strict=True):
     B("stllm_llama_layers_lora_scratch_bytes", [c_int] * 6, c_int64)
     B("stllm_llama_layers_lora", [ctypes.POINTER(LlamaLayersArgs), ctypes.POINTER(LlamaLayerWeights), ctypes.POINTER(LlamaLoraLayer), c_int, c_void_p])
     B("stllm_attention_offset_workspace_bytes", [c_int] * 4, c_int64)
+    B("stllm_attention_offset_ragged_workspace_bytes", [c_int] * 4, c_int64)
+    B("stllm_attention_offset_ragged", [c_int] + [c_void_p, c_int64, c_int64] * 4 + [c_int] * 5 + [c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
+    B("stllm_kv_append_spans", [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
     B("stllm_attention_offset", [c_int] + [c_void_p, c_int64, c_int64] * 4 + [c_int] * 5 + [c_float, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_llama_layers_extend", [ctypes.POINTER(LlamaLayersArgs), ctypes.POINTER(LlamaLayerWeights), c_int, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_gemv_w8", [ctypes.POINTER(GemvW8Args), c_void_p])
@@ -1046,6 +1050,35 @@ def attention_decode_ragged(q, k, v, kv_len, *, B, H, max_kv, D, scale, out=None
     return out
 
 
+def ragged_extend_available(device):
+    """attention_offset_ragged and kv_append_spans can serve tensors on `device`: a device check, nothing more — lib() binds strictly, so a library that
+    loads has both entry points.  LlamaModel.extend asks before it takes its ragged path, so that tensors off the device get the NotImplementedError the
+    call always raised, before anything is written; a stand-in for this module that states the two contracts answers for itself."""
+    return torch.device(device).type == "cuda"
+
+
+def attention_offset_ragged(q, k, v, q_off, kv_len, *, B, H, Sq, max_kv, D, scale, out=None, q_strides=None, k_strides=None, v_strides=None):
+    """stllm_attention_offset_ragged: up to Sq new query rows per batch row, each batch row behind its own number of cached positions (always causal).
+    q_off, kv_len: int32 [B] on the device — row b holds q_off[b] cached positions and n_b = kv_len[b] - q_off[b] (0 .. Sq) new ones, max_kv is the host-known
+    bound of kv_len; query row i < n_b sees key j iff j <= q_off[b] + i, the pad rows i >= n_b come out as zeros, K / V at or behind kv_len[b] are never read.
+    q / k / v: 2-D views with (batch, row) strides in elements, as for attention(q_off=), whose workspace pool this shares.  bf16 / fp16 / fp32 at D = 128
+    (fp32: max_kv <= 2048); anything else is an error (STLLM_ERR_UNSUPPORTED), not a fallback."""
+    td = q.dtype
+    _req(q_off, torch.int32, "q_off"); _req(kv_len, torch.int32, "kv_len")
+    if q_off.numel() != B or kv_len.numel() != B:
+        raise RuntimeError(f"attention_offset_ragged: q_off / kv_len have {q_off.numel()} / {kv_len.numel()} entries for B = {B}")
+    qs = q_strides if q_strides is not None else (Sq * q.stride(0), q.stride(0))
+    ks = k_strides if k_strides is not None else (max_kv * k.stride(0), k.stride(0))
+    vs = v_strides if v_strides is not None else (max_kv * v.stride(0), v.stride(0))
+    if out is None:
+        out = torch.empty((B * Sq, H * D), device=q.device, dtype=td)
+    ws = attention_offset_workspace(B, H, Sq, max_kv, q.device) if td != torch.float32 and D == 128 else None
+    _check(lib().stllm_attention_offset_ragged(dtype_code(td), _p(q), qs[0], qs[1], _p(k), ks[0], ks[1], _p(v), vs[0], vs[1],
+                                               _p(out), Sq * out.stride(0), out.stride(0), B, H, Sq, max_kv, D, scale, _p(q_off), _p(kv_len),
+                                               _p(ws), ws.numel() if ws is not None else 0, _stream()), "stllm_attention_offset_ragged")
+    return out
+
+
 def attention_shared(q, kp, vp, ks, vs, *, B, G, H, Sq, P, D, scale, max_sfx, sfx_len=None, sfx_q_off=0, causal=False, out=None,
                      q_strides=None, kp_strides=None, ks_strides=None):
     """stllm_attention_shared: B = G * R query rows, the R rows of group g read the P keys of prefix row g ONCE (kp / vp: 2-D views of the prefix buffer,
@@ -1083,6 +1116,19 @@ def kv_append_rows(src, cache, pos, *, with_q=False):
         raise RuntimeError(f"kv_append_rows: src {tuple(src.shape)}, cache {tuple(cache.shape)}, pos {tuple(pos.shape)}")
     _check(lib().stllm_kv_append_rows(dtype_code(cache.dtype), _p(src), src.stride(0), _p(cache), cache.stride(0), cache.stride(1), _p(pos), B, D3 // 3, max_len,
                                       int(with_q), _stream()), "stllm_kv_append_rows")
+    return cache
+
+
+def kv_append_spans(src, cache, pos0, n, *, S):
+    """stllm_kv_append_spans: cache[b, pos0[b] + i, cols] = src[b * S + i, cols] for i < min(n[b], S) and the [k | v] columns of the dense fused rows
+    src [B * S, 3*hidden]; cache: [B, max_len, 3*hidden], pos0 / n: int32 [B] on the device.  Pad rows, rows with n[b] = 0 and positions outside
+    [0, max_len) write nothing.  All compute dtypes."""
+    _req(src, cache.dtype, "src"); _req(pos0, torch.int32, "pos0"); _req(n, torch.int32, "n")
+    B, max_len, D3 = cache.shape
+    if src.shape != (B * S, D3) or pos0.numel() != B or n.numel() != B or cache.stride(2) != 1:
+        raise RuntimeError(f"kv_append_spans: src {tuple(src.shape)}, cache {tuple(cache.shape)}, pos0 {tuple(pos0.shape)}, n {tuple(n.shape)}, S {S}")
+    _check(lib().stllm_kv_append_spans(dtype_code(cache.dtype), _p(src), src.stride(0), _p(cache), cache.stride(0), cache.stride(1), _p(pos0), _p(n), B, S,
+                                       D3 // 3, max_len, _stream()), "stllm_kv_append_spans")
     return cache
 
 

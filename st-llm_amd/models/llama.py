@@ -431,7 +431,9 @@ class LlamaModel(nn.Module):
         the P+S cached keys with the query offset P (hip.attention(q_off=P)) -> o_proj -> MLP.  Sets cache.len = P + S; returns what prefill returns.
         P = 0 is prefill(cache=cache).  bf16 / fp16 / fp32; the split modes (bf16x3 / mixed) are not wired.
         lengths: suffixes of different lengths S_b <= S, right-padded to S, behind a uniform prefix — the cache becomes ragged (lens = P + S_b), the pad query
-        rows are don't-care.  Runs the per-op body on hip.attention(q_off=P, kv_len=P + S_b).  A ragged prefix takes one-token steps only (decode_step)."""
+        rows are don't-care.  Runs the per-op body on hip.attention(q_off=P, kv_len=P + S_b).
+        A RAGGED cache (cache.lens set), or a row with lengths[b] == 0, takes extend_ragged: row b appends its 0 <= S_b <= S tokens behind its own P_b
+        positions, a row with S_b == 0 is left exactly as it is."""
         cfg = self.config
         dt = runtime.compute_dtype()
         if runtime.gemm_split():
@@ -439,14 +441,14 @@ class LlamaModel(nn.Module):
         B, S, D = inputs_embeds.shape
         P = cache.len
         assert cache.batch == B and cache.qkv[0].dtype == dt
-        assert P + S <= cache.max_len, "KV cache full"
-        if cache.lens is not None:
-            raise NotImplementedError("LlamaModel.extend behind a ragged prefix (rows of different lengths): append one token at a time with decode_step")
         if lengths is not None:
             lengths = [int(n) for n in lengths]
-            assert len(lengths) == B and all(1 <= n <= S for n in lengths)
-            if len(set(lengths)) == 1 and lengths[0] == S:
-                lengths = None
+            assert len(lengths) == B and all(0 <= n <= S for n in lengths)
+        if cache.lens is not None or (lengths is not None and min(lengths) == 0):
+            return self.extend_ragged(inputs_embeds, cache, lengths)
+        assert P + S <= cache.max_len, "KV cache full"
+        if lengths is not None and len(set(lengths)) == 1 and lengths[0] == S:
+            lengths = None
         if P == 0:   # (a cache with a base holds P > 0 positions)
             mask = None if lengths is None else (torch.arange(S)[None, :] < torch.tensor(lengths)[:, None]).long()
             return self.prefill(inputs_embeds, mask, cache=cache)
@@ -489,6 +491,53 @@ class LlamaModel(nn.Module):
         for li, pk in enumerate(layers):
             decoder_layer(self, dt, x, pk, li, proj=proj, qkv_to=qkv_to, attn=attn, rope=(cos, sin), rope_seq=S)
         return x
+
+    def extend_ragged(self, inputs_embeds, cache, lengths=None):
+        """extend on a ragged cache: row b appends lengths[b] = S_b tokens (0 <= S_b <= S, right-padded to S; None: S for every row) behind the P_b positions it
+        holds (cache.lens[b], or cache.len).  The per-op decoder_layer body: the QKV GEMM + RoPE writes a dense [B * S, 3D] scratch — RoPE rows cos / sin[P_b + i],
+        gathered once per call, rope_seq = B * S —, hip.kv_append_spans copies the [k | v] columns of the live rows to positions P_b .. P_b + S_b - 1 of the cache,
+        hip.attention_offset_ragged reads q from the scratch and K / V from the cache (never behind P_b + S_b).  A row with S_b == 0 is untouched: nothing of
+        it is written, its K / V are not read.  The pad rows of the returned hidden states are don't-care but finite.  Sets cache.lens = P_b + S_b."""
+        cfg = self.config
+        dt = runtime.compute_dtype()
+        B, S, D = inputs_embeds.shape
+        H = cfg.num_attention_heads
+        hd = D // H
+        dev = inputs_embeds.device
+        if cache.base is not None:
+            raise NotImplementedError("LlamaModel.extend behind a ragged prefix on a shared base (rows of different lengths, or a row that appends nothing): "
+                                      "fork() the cache first")
+        if not hip.ragged_extend_available(dev):
+            raise NotImplementedError("LlamaModel.extend behind a ragged prefix (rows of different lengths, or a row that appends nothing) needs "
+                                      "hip.attention_offset_ragged / hip.kv_append_spans, which this backend does not provide for " + str(dev) +
+                                      ": append one token at a time with decode_step")
+        have = list(cache.lens) if cache.lens is not None else [cache.len] * B
+        new = [S] * B if lengths is None else lengths
+        assert all(p + n <= cache.max_len for p, n in zip(have, new)), "KV cache full"
+        layers = self.pack(dt)
+        x = inputs_embeds.reshape(B * S, D).float().clone()
+        cos, sin = self.rope(cache.max_len, dev)
+        # the pad rows take any valid position: the row's own next ones, clamped below max_len
+        pos = hip.h2d(torch.tensor([min(p + i, cache.max_len - 1) for p in have for i in range(S)], dtype=torch.int32), dev)
+        cos, sin = hip.gather_rows(cos, pos), hip.gather_rows(sin, pos)
+        q_off = hip.h2d(torch.tensor(have, dtype=torch.int32), dev)
+        n_new = hip.h2d(torch.tensor(new, dtype=torch.int32), dev)
+        kv_len = hip.h2d(torch.tensor([p + n for p, n in zip(have, new)], dtype=torch.int32), dev)
+        max_kv = max(1, max(p + n for p, n in zip(have, new)))
+        dense = torch.empty((B * S, 3 * D), device=dev, dtype=dt)
+        strides = cache.kv(0)[2]
+
+        def attn(li, dense):
+            hip.kv_append_spans(dense, cache.qkv[li], q_off, n_new, S=S)
+            k, v, _ = cache.kv(li)
+            return hip.attention_offset_ragged(dense[:, :D], k, v, q_off, kv_len, B=B, H=H, Sq=S, max_kv=max_kv, D=hd, scale=hd ** -0.5,
+                                               q_strides=(S * 3 * D, 3 * D), k_strides=strides, v_strides=strides)
+        proj = gemm_proj(layers, dt, True)
+        for li, pk in enumerate(layers):
+            decoder_layer(self, dt, x, pk, li, proj=proj, qkv_to=lambda li: {"out": dense}, attn=attn, rope=(cos, sin), rope_seq=B * S)
+        cache.set_lens([p + n for p, n in zip(have, new)])
+        h16, h32 = hip.rmsnorm(x, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
+        return h32.view(B, S, D), h16
 
     def extend_layers_shared(self, x, layers, B, S, pos, cos, sin, cache, dt, lengths=None):
         """extend's layer loop for a cache with a shared base (KVCache.share): the S new rows sit at the local positions [off, off + S), off = pos - base_len,

@@ -799,7 +799,7 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
     def generate(self, inputs_embeds=None, max_new_tokens=16, num_beams=1, do_sample=False, stopping_criteria=None,
                  attention_mask=None, use_cache=True, min_length=0, top_p=1.0, repetition_penalty=1.0, length_penalty=1.0,
                  temperature=1.0, eos_token_id=2, pad_token_id=0, generator=None, prefix_cache=None, batching="groups", stop_sequences=None,
-                 return_lengths=False, share_prefix=False, selection="torch", sync_every=1, **unused):
+                 return_lengths=False, share_prefix=False, selection="torch", sync_every=1, return_cache=False, **unused):
         """`llama_model.generate(inputs_embeds=..., ...)` as Chat.answer calls it (conversation.py:231-243; demo.py runs
         num_beams=5, do_sample=False): HIP prefill of `inputs_embeds` into a KV cache, then one decode step per token with
         HF's greedy / sampling / beam-search bookkeeping restated in stllm_amd/generation.py.  eos / pad default to the
@@ -810,12 +810,16 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
         sends: a padded batch rejects it; batching="ragged" accepts both together (below).
         batching: "groups" (default) serves a padded batch by length groups, one decode loop per distinct length; "ragged" serves it in ONE batched call on a
         ragged KV cache (KVCache.lens) — every row still generates exactly as its unpadded prompt would alone.  Left-padded rows are shifted
-        to right-padded first.  With prefix_cache the prefix may hold one row shared by all prompts (N questions about one video) or one row per prompt.
+        to right-padded first.  With prefix_cache the prefix may hold one row shared by all prompts (N questions about one video) or one row per prompt —
+        and a per-prompt prefix may be ragged itself (KVCache.lens: different videos, or the rows of an earlier batch).
         stop_sequences / return_lengths: see generation.generate (per-row stop; the number of generated tokens per row).
         share_prefix: rows with the same first positions (questions behind one prefix row, the beams of a prompt) read one physical copy of them instead of
         owning one each (generation.generate).  Opt-in; needs use_cache.
         selection / sync_every: "device" selects every token with the project's own kernels and keeps the ids on the device (generation.generate;
-        DESIGN.md §4.2f).  Opt-in; "torch" (default) is the path as it always was."""
+        DESIGN.md §4.2f).  Opt-in; "torch" (default) is the path as it always was.
+        return_cache: also return a generation.Continuation(cache, pending) as the last element of the result — the working KV cache cut to every row's own
+        tokens and the row's last, not yet fed id — from which a later call continues (Chat.follow_up).  num_beams == 1, use_cache, one batched call (not the
+        length groups of batching="groups")."""
         from .. import generation
         if batching not in ("groups", "ragged"):
             raise ValueError(f"generate(batching={batching!r}): 'groups' or 'ragged'")
@@ -823,7 +827,7 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
                                   temperature=temperature, repetition_penalty=repetition_penalty, length_penalty=length_penalty,
                                   stopping_criteria=stopping_criteria, eos_token_id=eos_token_id, pad_token_id=pad_token_id, use_cache=use_cache,
                                   generator=generator, stop_sequences=stop_sequences, return_lengths=return_lengths, share_prefix=share_prefix,
-                                  selection=selection, sync_every=sync_every)
+                                  selection=selection, sync_every=sync_every, return_cache=return_cache)
         B, S = inputs_embeds.shape[:2]
         spans = [(0, S)] * B if attention_mask is None or (batching == "groups" and B == 1) else _prompt_spans(attention_mask, batching)
         lengths = [n for _, n in spans]
@@ -845,6 +849,8 @@ class STLLMForCausalLM(LlamaForCausalLM, BaseModel):
         if padded:
             if prefix_cache is not None:
                 raise NotImplementedError("generate(prefix_cache=...) with a padded batch: a prefix serves equal-length prompts only")
+            if return_cache:
+                raise NotImplementedError("generate(return_cache=True) with a padded batch: batching='ragged' keeps the rows in one cache")
             # Ragged prompts (round 5).  The device KV cache holds equal-length rows (one position counter, RoPE by row index), and the reference itself only
             # ever sends one prompt x beams (conversation.py:231-243) — so a padded batch is served by LENGTH GROUPS: HF derives position_ids from the mask
             # (positions count real tokens only), i.e. every row generates exactly as its unpadded prompt would alone; rows of equal length share one

@@ -110,6 +110,68 @@ if "--shared" in sys.argv:
         print(f"shared-prefix decode attention R={R:3d} P={P:5d} sfx={sfx:4d}: shared {fmt('shared')}  copies {fmt('copies')}  prefix-only key-split+merge {fmt('split')}"
               f"  K/V bytes shared {(P + R * sfx) * 2 * H * D * 2 / 1e6:.1f} MB vs copies {R * (P + sfx) * 2 * H * D * 2 / 1e6:.1f} MB", flush=True)
     sys.exit(0)
+if "--ragged-suffix" in sys.argv:
+    # --ragged-suffix P1,P2,...:n1,n2,... (repeatable): a block of n_b new rows behind P_b cached positions per batch row (LlamaModel.extend on a ragged cache).
+    #   ragged  : hip.attention_offset_ragged with the key split forced on (1), forced off (0) and by the rule (auto), padded to Sq = max(n);
+    #   per-row : what the parent commit has — one stllm_attention_offset call per row with n_b > 0 (B = 1, q_off = P_b, default dispatch), len(rows) launches (pairs);
+    #   steps   : ... or max(n) one-token ragged decode-attention steps over all rows (kv_len = P_b + min(t + 1, n_b)).
+    # Same process and buffers, alternating, every timing a captured graph of 20 calls; best of 5 replays, every round printed.
+    def timed_r(fn, rounds=5):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(20):
+                fn()
+        g.replay(); torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        best = float("inf")
+        for _ in range(rounds):
+            s.record(); g.replay(); e.record(); torch.cuda.synchronize()
+            best = min(best, s.elapsed_time(e) / 20 * 1e3)
+        return best
+    H, D, dt = 32, 128, torch.bfloat16
+    HD, W = H * D, 3 * H * D
+    for spec in [sys.argv[i + 1] for i, a in enumerate(sys.argv) if a == "--ragged-suffix"]:
+        Ps, ns = (list(map(int, part.split(","))) for part in spec.split(":"))
+        assert len(Ps) == len(ns)
+        B, S, max_kv = len(Ps), max(ns), max(p + n for p, n in zip(Ps, ns))
+        ML = max_kv + 8
+        buf = torch.randn(B * ML, W, device="cuda").to(dt)
+        dense = torch.randn(B * S, W, device="cuda").to(dt)
+        st = (ML * W, W)
+        out = torch.empty(B * S, HD, device="cuda", dtype=dt)
+        q_off = torch.tensor(Ps, dtype=torch.int32).cuda()
+        kv_len = torch.tensor([p + n for p, n in zip(Ps, ns)], dtype=torch.int32).cuda()
+        step_len = [torch.tensor([p + min(t + 1, n) for p, n in zip(Ps, ns)], dtype=torch.int32).cuda() for t in range(S)]
+        ragged = lambda: hip.attention_offset_ragged(dense[:, :HD], buf[:, HD:2 * HD], buf[:, 2 * HD:], q_off, kv_len, B=B, H=H, Sq=S, max_kv=max_kv, D=D,
+                                                     scale=D ** -0.5, out=out, q_strides=(S * W, W), k_strides=st, v_strides=st)
+
+        def per_row():
+            for b, (p, n) in enumerate(zip(Ps, ns)):
+                if n:
+                    hip.attention(dense[b * S:, :HD], buf[b * ML:, HD:2 * HD], buf[b * ML:, 2 * HD:], B=1, H=H, Sq=n, Skv=p + n, D=D, scale=D ** -0.5, causal=True,
+                                  q_strides=(S * W, W), k_strides=st, v_strides=st, q_off=p, out=out[b * S:b * S + n])
+
+        def steps():
+            for t in range(S):
+                hip.attention(dense[t:, :HD], buf[:, HD:2 * HD], buf[:, 2 * HD:], B=B, H=H, Sq=1, Skv=max_kv, D=D, scale=D ** -0.5, kv_len=step_len[t],
+                              q_strides=(S * W, W), k_strides=st, v_strides=st, out=out[:B])
+        res = {}
+        try:
+            for rnd in range(2):
+                for name, opt, f in (("split", 1, ragged), ("tile", 0, ragged), ("auto", -1, ragged), ("per-row", -1, per_row), ("steps", -1, steps)):
+                    hip.set_option("attn_ksplit", opt)
+                    res.setdefault(name, []).append(timed_r(f))
+        finally:
+            hip.set_option("attn_ksplit", -1)
+        ragged()
+        auto = hip.lib().stllm_last_kernel().decode()
+        fmt = lambda n: f"{min(res[n]):7.1f} us (" + " ".join(f"{x:.1f}" for x in res[n]) + ")"
+        print(f"ragged suffix B={B} P={','.join(map(str, Ps))} n={','.join(map(str, ns))}: key-split {fmt('split')}  tile {fmt('tile')}  auto {fmt('auto')} -> {auto}"
+              f"  | parent: per-row offset calls {fmt('per-row')}  {S} decode steps {fmt('steps')}", flush=True)
+    sys.exit(0)
 if "--suffix" in sys.argv:
     # LlamaModel.extend's shape: Sq new rows behind q_off cached ones, operands addressed inside one fused cache buffer as the model passes them.
     # The offset tile kernel (attn_ksplit = 0) and the key-split pair (1) on the same buffers, same process, alternating; "auto" is the dispatch rule.

@@ -13,7 +13,7 @@ r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std
 cur = None
 rows = {}
 for line in r.stderr.splitlines():
-    m = re.search(r"remark:\s+(Function Name|SGPRs Spill|VGPRs Spill|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs):\s*(\S+)", line)
+    m = re.search(r"remark:\s+(Function Name|SGPRs Spill|VGPRs Spill|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]|TotalSGPRs|SGPRs):\s*(\S+)", line)
     if not m:
         continue
     k, v = m.group(1), m.group(2)
@@ -21,14 +21,14 @@ for line in r.stderr.splitlines():
         cur = v
         rows[cur] = {}
     elif cur:
-        rows[cur][k.replace(' [bytes/lane]', '').replace(' [waves/SIMD]', '')] = v
+        rows[cur][k.replace('TotalSGPRs', 'SGPRs').replace(' [bytes/lane]', '').replace(' [waves/SIMD]', '').replace(' [bytes/block]', '')] = v
 dem = subprocess.run(["c++filt"] + list(rows), capture_output=True, text=True).stdout.splitlines()
 for name, d in zip(dem, rows.values()):
     name = re.sub(r"\(anonymous namespace\)::", "", name).split("(")[0].replace("void ", "")
     if flt and flt not in name:
         continue
     print(f"{name:70s} vgpr {d.get('VGPRs', '?'):>4} agpr {d.get('AGPRs', '?'):>4} sgpr {d.get('SGPRs', '?'):>4} scratch {d.get('ScratchSize', '?'):>5} "
-          f"vgpr-spill {d.get('VGPRs Spill', '?'):>4} sgpr-spill {d.get('SGPRs Spill', '?'):>4}")
+          f"vgpr-spill {d.get('VGPRs Spill', '?'):>4} sgpr-spill {d.get('SGPRs Spill', '?'):>4} lds {d.get('LDS Size', '?'):>6} occupancy {d.get('Occupancy', '?'):>2}")
 if r.returncode:
     print(r.stderr[-3000:])
     sys.exit(r.returncode)

@@ -9,6 +9,12 @@
 Device clock / power over the whole timed region come from bench.py's Telemetry.
 
     python tools/prefix_bench.py [--layers 32] [--nv 512 2048] [--question 40] [--new 16] [--rounds 5] [--mode bf16]
+
+--follow-up [--rows 4]: a follow-up round of N conversations in one ragged batch (Chat.follow_up's generate call) against re-prefilling every row's whole
+history — N rows whose histories (video of --nv[0] tokens + earlier turns) have different lengths, a next turn of a different length per row:
+  (a) re-prefill   generate(inputs_embeds = history | turn of every row, batching="ragged"): one ragged prefill of everything, on every turn
+  (b) follow-up    generate(inputs_embeds = turn of every row, prefix_cache = the rows' ragged history cache, batching="ragged"): fork + ONE ragged extend
+and the fork() copy of (b) on its own.
 """
 import argparse
 import os
@@ -39,6 +45,8 @@ def main():
     ap.add_argument("--mode", default="bf16")
     ap.add_argument("--share-prefix", action="store_true", help="add (d): first token / answer with the prefix SHARED (KVCache.share, generate(share_prefix=True)) "
                                                                 "instead of forked: no copy of the prefix rows, the shared-prefix attention kernels")
+    ap.add_argument("--follow-up", action="store_true", help="time a follow-up round of --rows conversations against re-prefilling every row's whole history")
+    ap.add_argument("--rows", type=int, default=4)
     a = ap.parse_args()
     import stllm_amd  # noqa: F401
     import bench
@@ -53,6 +61,10 @@ def main():
     q_emb = synth.normal_(torch.empty((1, Q, 4096), device="cuda"), "bench.question", 0, 0.05)
     kw = dict(max_new_tokens=N, num_beams=1, do_sample=False, eos_token_id=None)
     tele = bench.Telemetry(0).start()
+    if a.follow_up:
+        follow_up(a, m, kw, wall)
+        print(f"\ntelemetry: {tele.stop()}")
+        return
     rows = []
     for nv in a.nv:
         v_emb = synth.normal_(torch.empty((1, nv, 4096), device="cuda"), f"bench.video{nv}", 0, 0.05)
@@ -109,6 +121,46 @@ def main():
               f"{med['ans_a']:.2f} ({best['ans_a']:.2f}) | {med['ans_b']:.2f} ({best['ans_b']:.2f}) | {derived:.2f} | {tv:.2f} |")
     print(f"\ntelemetry: {telemetry}")
     print("(c) answer = its first-token time + the decode steps of (a): the decode loop behind the first token is the same code for all three.")
+
+
+def follow_up(a, m, kw, wall):
+    from stllm_amd import synth
+    lm = m.model
+    B, nv, N = a.rows, a.nv[0], a.new
+    hist = [nv + (60, 95, 130, 75, 110, 66, 142, 88)[b % 8] for b in range(B)]       # video + question + first answer, per row
+    turn = [(12, 30, 8, 21, 40, 16, 9, 27)[b % 8] for b in range(B)]
+    emb = synth.normal_(torch.empty((B, max(h + t for h, t in zip(hist, turn)), 4096), device="cuda"), "bench.dialogue", 0, 0.05)
+
+    def padded(spans):
+        L = max(n for _, n in spans)
+        x = torch.zeros((B, L, 4096), device="cuda")
+        for b, (first, n) in enumerate(spans):
+            x[b, :n] = emb[b, first:first + n]
+        return x, (torch.arange(L)[None, :] < torch.tensor([n for _, n in spans])[:, None]).long()   # (the mask stays on the host: no D2H read per call)
+    h_emb, h_mask = padded([(0, h) for h in hist])
+    cache = lm.new_cache(B, max(hist), "cuda")
+    lm.prefill(h_emb, h_mask, cache=cache)                                            # the state a Dialogue holds between turns: a ragged cache
+    assert cache.lens == hist
+    w_emb, w_mask = padded([(0, h + t) for h, t in zip(hist, turn)])
+    t_emb, t_mask = padded(list(zip(hist, turn)))
+    room = max(hist) + max(turn) + N
+    fns = dict(reprefill=lambda: m.generate(inputs_embeds=w_emb, attention_mask=w_mask, batching="ragged", **kw),
+               follow_up=lambda: m.generate(inputs_embeds=t_emb, attention_mask=t_mask, prefix_cache=cache, batching="ragged", **kw),
+               fork=lambda: cache.fork(max_len=room),
+               extend=lambda: lm.extend(t_emb, cache.fork(max_len=room), lengths=turn))
+    ids_a, ids_b = fns["reprefill"](), fns["follow_up"]()                             # warm-up of every path + a sanity line
+    fns["extend"]()
+    same = int((ids_a == ids_b).sum())
+    t = {k: [] for k in fns}
+    for _ in range(a.rounds):
+        for k, fn in fns.items():
+            t[k].append(wall(fn))
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    best = {k: min(v) for k, v in t.items()}
+    gb = sum(hist) * 2 * 4096 * 2 * a.layers / 1e9
+    print(f"[prefix_bench --follow-up] {a.layers} layers, {a.mode}, rows={B} history={hist} turn={turn} new={N}: " +
+          "  ".join(f"{k} {med[k]:.2f} ms (best {best[k]:.2f})" for k in fns) +
+          f"  | fork copies {gb:.2f} GB of live K / V (whole [q | k | v] rows: x 1.5)  | follow-up ids == re-prefill ids on {same}/{ids_a.numel()} tokens", flush=True)
 
 
 if __name__ == "__main__":
