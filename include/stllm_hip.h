@@ -600,6 +600,45 @@ int stllm_kv_append_spans(int dtype, const void* src, int64_t ld_src, void* cach
                           const int32_t* pos0, const int32_t* n, int B, int S, int hidden, int max_len, void* stream);
 
 /*
+ * stllm_attention_offset_ragged on a PACKED query buffer (additive to ABI 7; always causal): R segments, the step of a serving loop that carries one token for
+ * every running request and a whole prompt for a newly admitted one (LlamaModel.step_segments).  q and out hold T packed rows (row strides q_rs / o_rs, no
+ * batch stride); K / V are the rows of a cache of n_slots rows (k_bs / v_bs between cache rows).  slot, row0, q_off, kv_len: int32 [R] in device memory:
+ *   slot[r]    cache row of segment r (K / V base = slot[r] * k_bs)
+ *   row0[r]    first packed row of the segment (q / out base = row0[r] * q_rs / o_rs)
+ *   q_off[r]   cached positions in front of the segment
+ *   kv_len[r]  q_off[r] + n_r, n_r the segment's new rows; clamped as stllm_attention_offset_ragged clamps them (kv_len to [0, max_kv], q_off to
+ *              [0, kv_len], n_r to [0, max_n])
+ * Query row i < n_r of segment r is packed row row0[r] + i, sits at position q_off[r] + i and sees key j of cache row slot[r] iff j <= q_off[r] + i.
+ * max_n bounds n_r and sizes the query-tile grid, max_kv bounds kv_len.  The host keeps slots distinct and in range and the segments' packed rows disjoint;
+ * on top of that the kernels guard the tables: a segment with slot[r] outside [0, n_slots), row0[r] < 0 or row0[r] + n_r > T does nothing at all.
+ * Coverage, dispatch rule, "attn_ksplit" forcing, workspace size and stllm_last_kernel() are those of stllm_attention_offset_ragged, the plan evaluated at
+ * (R, H, max_n, max_kv); anything else returns STLLM_ERR_UNSUPPORTED.  With slot[r] = r, row0[r] = r * Sq, every n_r = Sq = max_n and T = R * Sq the output
+ * is bit-identical to stllm_attention_offset_ragged(B = R) under the same forced "attn_ksplit" (0 / 1); the same call twice gives the same bits.
+ * Memory regions.  Never read: K / V at or behind kv_len[r]; every cache row not named by a live segment; packed q rows that belong to no live segment's
+ * [row0[r], row0[r] + n_r) — a pad lane of a query tile loads zeros, not the neighbouring segment's row —, rows at or behind T among them.  Written: exactly
+ * the packed out rows row0[r] + i, i < n_r, of live segments, at columns [0, H * 128); no pad row, no zero row, nothing else.  Workspace: every record the
+ * merge reads was written by the partial pass of the same call (pad rows leave no record and the merge reads none).
+ */
+int64_t stllm_attention_segments_workspace_bytes(int R, int H, int max_n, int max_kv);
+int stllm_attention_segments(int dtype, const void* q, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v, int64_t v_bs,
+                             int64_t v_rs, void* out, int64_t o_rs, int R, int H, int D, int T, int n_slots, int max_n, int max_kv, float scale,
+                             const int32_t* slot, const int32_t* row0, const int32_t* q_off, const int32_t* kv_len, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+
+/*
+ * stllm_kv_append_spans for a PACKED source (additive to ABI 7).  slot, row0, pos0, n: int32 [R] in device memory.  For every segment r and every
+ * i < n[r] (n[r] <= max_n, which sizes the grid) with 0 <= pos0[r] + i < max_len the [k | v] columns of the packed fused row src[(row0[r] + i)*ld_src ..
+ * + 3*hidden) are copied to cache[slot[r]*batch_stride + (pos0[r] + i)*row_stride + the same columns], 16 bytes per lane.  A segment with slot[r] outside
+ * [0, n_slots), row0[r] < 0 or row0[r] + n[r] > T writes nothing.  Dtypes, strides and alignment as for stllm_kv_append_rows; R, max_n <= 65535.  With
+ * slot[r] = r and row0[r] = r * S the result is bit-identical to stllm_kv_append_spans.
+ * Memory regions.  Never read: the q columns of src, packed rows outside the live segments.  Never written: the q columns of the cache, any cache row not
+ * named by a segment, any position other than pos0[r] + i, i < n[r], of a named one, anything behind max_len.
+ */
+int stllm_kv_append_segments(int dtype, const void* src, int64_t ld_src, void* cache, int64_t batch_stride, int64_t row_stride,
+                             const int32_t* slot, const int32_t* row0, const int32_t* pos0, const int32_t* n, int R, int T, int n_slots,
+                             int max_n, int hidden, int max_len, void* stream);
+
+/*
  * Row gather (token-block assembly, dynamic masking, residual-index selection, embedding lookup):
  *   dst[i, :] = scale * ((idx_a[i] >= 0 ? src_a[idx_a[i], :] : src_b[-idx_a[i]-1, :]) + (add ? add[idx_add[i], :] : 0))
  * all f32, D % 4 == 0.  The same kernel re-orders tokens between the BT-Adapter's spatial '(b t) p' and temporal

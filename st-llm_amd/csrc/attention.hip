@@ -41,8 +41,13 @@ struct AttnParams {
 // stllm_attention_offset_ragged: the RAGGED instantiations take the query offset PER BATCH ROW on top (with kv_len: row b holds q_off_tab[b] cached positions
 // and kv_len[b] - q_off_tab[b] new ones).  A type of its own, so that the kernel arguments of every other instantiation stay what they were.
 struct AttnRaggedParams : AttnParams { const int32_t* q_off_tab; };
-template <bool RAGGED> struct AttnParamsOf { using type = AttnParams; };
-template <> struct AttnParamsOf<true> { using type = AttnRaggedParams; };
+// stllm_attention_segments: the SEG instantiations (RAGGED on top) read a PACKED query buffer: "batch row" r is a segment whose K / V sit in cache row slot[r]
+// and whose n_r query / output rows are the packed rows row0[r] .. row0[r] + n_r - 1 (q_bs / o_bs unused: the bases are row0[r] * q_rs / o_rs); T packed
+// rows, n_slots cache rows.  Again a type of its own: the arguments of every other instantiation stay what they were.
+struct AttnSegParams : AttnRaggedParams { const int32_t* slot; const int32_t* row0; int T, n_slots; };
+template <bool RAGGED, bool SEG = false> struct AttnParamsOf { using type = AttnParams; };
+template <> struct AttnParamsOf<true, false> { using type = AttnRaggedParams; };
+template <> struct AttnParamsOf<true, true> { using type = AttnSegParams; };
 
 // the per-row tables of the RAGGED instantiations, clamped: 0 <= q_off <= kvlen <= Skv and n = kvlen - q_off <= Sq new rows.  A row without new positions
 // (n == 0) gets kvlen = 0: its workgroups walk no key and load nothing.  b is workgroup-uniform, so all three live in scalar registers.
@@ -59,6 +64,28 @@ __device__ __forceinline__ RaggedRow ragged_row(const AttnRaggedParams& p, int b
 __device__ __forceinline__ RaggedRow ragged_row(const AttnParams& p, int b) {
   return RaggedRow{p.q_off, p.kv_len ? min(p.kv_len[b], p.Skv) : p.Skv, p.Sq};
 }
+
+// a segment of the SEG instantiations: ragged_row's clamps, then the table guard — a slot outside [0, n_slots) or packed rows outside [0, T) make the segment
+// empty (n = 0, kvlen = 0: its workgroups walk no key, load nothing and store nothing), so that a bad table cannot reach memory outside the buffers.
+struct SegRow : RaggedRow { int slot, row0; };
+__device__ __forceinline__ SegRow seg_row(const AttnSegParams& p, int r) {
+  SegRow s;
+  static_cast<RaggedRow&>(s) = ragged_row(static_cast<const AttnRaggedParams&>(p), r);
+  s.slot = p.slot[r];
+  s.row0 = p.row0[r];
+  if (s.slot < 0 || s.slot >= p.n_slots || s.row0 < 0 || (int64_t)s.row0 + s.n > p.T) { s.n = 0; s.kvlen = 0; s.slot = 0; s.row0 = 0; }
+  return s;
+}
+// where a batch row's K / V, query and output rows start (batch index / elements) and how many query rows exist in memory: the batch strides for every
+// instantiation but SEG, the segment's tables for SEG.  Used in place, where the addresses are formed, so that the code of the other instantiations stays what it was.
+template <typename P> __device__ __forceinline__ int attn_kv_row(const P&, RaggedRow, int b) { return b; }
+template <typename P> __device__ __forceinline__ int attn_kv_row(const P&, SegRow s, int) { return s.slot; }
+template <typename P> __device__ __forceinline__ int64_t attn_q_base(const P& p, RaggedRow, int b) { return (int64_t)b * p.q_bs; }
+template <typename P> __device__ __forceinline__ int64_t attn_q_base(const P& p, SegRow s, int) { return (int64_t)s.row0 * p.q_rs; }
+template <typename P> __device__ __forceinline__ int64_t attn_o_base(const P& p, RaggedRow, int b) { return (int64_t)b * p.o_bs; }
+template <typename P> __device__ __forceinline__ int64_t attn_o_base(const P& p, SegRow s, int) { return (int64_t)s.row0 * p.o_rs; }
+template <typename P> __device__ __forceinline__ int attn_q_rows(const P& p, RaggedRow) { return p.Sq; }
+template <typename P> __device__ __forceinline__ int attn_q_rows(const P&, SegRow s) { return s.n; }
 
 constexpr float kNeg = -1.0e30f;
 
@@ -95,8 +122,10 @@ constexpr int kSplRec = 132;   // floats per partial record: O[128], m (raw-scor
 // LIVE (the suffix pass of stllm_attention_shared only): key rows at or behind the batch row's kv_len are not LOADED (zeros instead) — the rows behind a
 // suffix's length are uninitialised memory, and a masked score of 0 times a NaN in V would reach the output.  Every other instantiation has LIVE = false
 // and compiles to what it always was.
-template <typename T, int DP, int NW, bool SPLIT = false, bool LIVE = false, bool RAGGED = false>
-__global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const typename AttnParamsOf<RAGGED>::type p) {
+// SEG (stllm_attention_segments, RAGGED on top): blockIdx.z is a segment of a packed query buffer.  A pad query row (i >= n_r) does not exist there — packed row
+// row0 + i belongs to another segment or lies behind T —, so it is neither loaded (zeros) nor stored, as output or as a key-split record.
+template <typename T, int DP, int NW, bool SPLIT = false, bool LIVE = false, bool RAGGED = false, bool SEG = false>
+__global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const typename AttnParamsOf<RAGGED, SEG>::type p) {
   constexpr int KS = DP / 16;          // k-steps of the S^T MFMA chain
   constexpr int DB = DP / 32;          // 32-row blocks of O^T
   constexpr int KPITCH = DP * 2 + 16;  // bytes per K row in LDS
@@ -117,7 +146,8 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const typename AttnP
   const int qrow = q_blk0 + wave * 32 + li;  // this lane's query
   const int D = p.D;
   static_assert(!RAGGED || LIVE, "the rows behind a ragged row's length are uninitialised: live loads only");
-  const RaggedRow rr = ragged_row(p, b);
+  static_assert(!SEG || RAGGED, "segments are ragged rows of a packed buffer");
+  const auto rr = [&] { if constexpr (SEG) return seg_row(p, b); else return ragged_row(p, b); }();
   const int kvlen = rr.kvlen;
   // the query offset, read where it is used: per batch row (RAGGED) or the call's (every other instantiation, whose code this keeps what it was)
 #define ATTN_Q_OFF (RAGGED ? rr.q_off : p.q_off)
@@ -126,12 +156,12 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const typename AttnP
   // ---- Q fragments (B operand of S^T): lane holds Q[q][ks*16 + lh*8 .. +8] ------------------------
   i32x4 qf[KS];
   {
-    const char* qp = p.q + ((int64_t)b * p.q_bs + (int64_t)(qrow < p.Sq ? qrow : 0) * p.q_rs + (int64_t)h * D) * 2;
+    const char* qp = p.q + (attn_q_base(p, rr, b) + (int64_t)(qrow < attn_q_rows(p, rr) ? qrow : 0) * p.q_rs + (int64_t)h * D) * 2;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int d0 = ks * 16 + lh * 8;
       i32x4 z = {0, 0, 0, 0};
-      qf[ks] = (qrow < p.Sq && d0 < D) ? *reinterpret_cast<const i32x4*>(qp + d0 * 2) : z;
+      qf[ks] = (qrow < attn_q_rows(p, rr) && d0 < D) ? *reinterpret_cast<const i32x4*>(qp + d0 * 2) : z;
     }
   }
 
@@ -149,8 +179,8 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const typename AttnP
   if constexpr (RAGGED) {
     if (q_blk0 >= n_new) kv_end = 0;   // every query row of this workgroup is pad: it walks no key, loads nothing and stores its zeros / empty records
   }
-  const char* kbase = p.k + ((int64_t)b * p.k_bs + (int64_t)h * D) * 2;
-  const char* vbase = p.v + ((int64_t)b * p.v_bs + (int64_t)h * D) * 2;
+  const char* kbase = p.k + ((int64_t)attn_kv_row(p, rr, b) * p.k_bs + (int64_t)h * D) * 2;
+  const char* vbase = p.v + ((int64_t)attn_kv_row(p, rr, b) * p.v_bs + (int64_t)h * D) * 2;
 
   // K/V tiles are register-staged one tile AHEAD: the global loads of tile t+1 are issued before the MFMA/softmax work of
   // tile t and only consumed (written to LDS) at the top of the next iteration — HBM/L2 latency hides under compute.
@@ -259,7 +289,7 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const typename AttnP
   // ---- normalise and store: lane holds O[q][d = i*32 + (r&3) + 8*(r>>2) + 4*lh] ------------------------
   if constexpr (SPLIT) {
     static_assert(!SPLIT || DP == 128, "the partial records hold 128 dims");
-    if (qrow < p.Sq) {
+    if (qrow < attn_q_rows(p, rr)) {   // SEG: a pad row leaves no record (the merge does not read one)
       // a row that saw no key of this range (its tiles skipped, or every key of them masked) has m_run == kNeg and, where a tile was walked for the
       // sake of the wave's other rows, exp2(0) weights in l / O: its record is the empty state, which the merge weighs with exactly 0
       bool empty = m_run <= 0.5f * kNeg;
@@ -277,9 +307,9 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_kernel(const typename AttnP
     }
     return;
   }
-  if (qrow < p.Sq) {
+  if (qrow < attn_q_rows(p, rr)) {
     const float inv = 1.0f / l_run;
-    uint16_t* op = reinterpret_cast<uint16_t*>(p.o) + (int64_t)b * p.o_bs + (int64_t)qrow * p.o_rs + (int64_t)h * D;
+    uint16_t* op = reinterpret_cast<uint16_t*>(p.o) + attn_o_base(p, rr, b) + (int64_t)qrow * p.o_rs + (int64_t)h * D;
 #pragma unroll
     for (int i = 0; i < DB; ++i) {
 #pragma unroll
@@ -1067,8 +1097,9 @@ int launch_dma(const AttnParams& p, hipStream_t stream, int nw_req) {
 constexpr int kF32MaxKv = 2048;
 
 // RAGGED (attn_f32_ragged_kernel, stllm_attention_offset_ragged): offset and length per batch row; a pad row is written as zeros and reads no key.
-template <bool RAGGED>
-__device__ __forceinline__ void attn_f32_body(const typename AttnParamsOf<RAGGED>::type& p) {
+// SEG (attn_f32_segments_kernel, stllm_attention_segments): a segment of a packed buffer; a pad row does not exist, so it is neither read nor written.
+template <bool RAGGED, bool SEG = false>
+__device__ __forceinline__ void attn_f32_body(const typename AttnParamsOf<RAGGED, SEG>::type& p) {
   __shared__ float q_s[4][128];
   __shared__ float sc[4][kF32MaxKv];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1076,9 +1107,12 @@ __device__ __forceinline__ void attn_f32_body(const typename AttnParamsOf<RAGGED
   const int qrow = blockIdx.x * 4 + w;
   if (qrow >= p.Sq) return;  // no block-level sync below
   const int D = p.D;
-  const RaggedRow rr = ragged_row(p, b);
+  const auto rr = [&] { if constexpr (SEG) return seg_row(p, b); else return ragged_row(p, b); }();
   const int kvlen = rr.kvlen;
-  if constexpr (RAGGED) {
+  if constexpr (SEG) {
+    if (qrow >= rr.n) return;
+  }
+  if constexpr (RAGGED && !SEG) {
     if (qrow >= rr.n) {
       float* o = reinterpret_cast<float*>(p.o) + (int64_t)b * p.o_bs + (int64_t)qrow * p.o_rs + (int64_t)h * p.D;
       for (int d = lane; d < p.D; d += 64) o[d] = 0.0f;
@@ -1086,9 +1120,9 @@ __device__ __forceinline__ void attn_f32_body(const typename AttnParamsOf<RAGGED
     }
   }
   const int kv_end = p.causal ? min(kvlen, (RAGGED ? rr.q_off : p.q_off) + qrow + 1) : kvlen;
-  const float* q = reinterpret_cast<const float*>(p.q) + (int64_t)b * p.q_bs + (int64_t)qrow * p.q_rs + (int64_t)h * D;
-  const float* kb = reinterpret_cast<const float*>(p.k) + (int64_t)b * p.k_bs + (int64_t)h * D;
-  const float* vb = reinterpret_cast<const float*>(p.v) + (int64_t)b * p.v_bs + (int64_t)h * D;
+  const float* q = reinterpret_cast<const float*>(p.q) + attn_q_base(p, rr, b) + (int64_t)qrow * p.q_rs + (int64_t)h * D;
+  const float* kb = reinterpret_cast<const float*>(p.k) + (int64_t)attn_kv_row(p, rr, b) * p.k_bs + (int64_t)h * D;
+  const float* vb = reinterpret_cast<const float*>(p.v) + (int64_t)attn_kv_row(p, rr, b) * p.v_bs + (int64_t)h * D;
   for (int d = lane; d < D; d += 64) q_s[w][d] = q[d];
   __builtin_amdgcn_wave_barrier();
   float mx = kNeg;
@@ -1116,7 +1150,7 @@ __device__ __forceinline__ void attn_f32_body(const typename AttnParamsOf<RAGGED
   sum = wave_sum(sum);
   __builtin_amdgcn_wave_barrier();
   const float inv = 1.0f / sum;
-  float* o = reinterpret_cast<float*>(p.o) + (int64_t)b * p.o_bs + (int64_t)qrow * p.o_rs + (int64_t)h * D;
+  float* o = reinterpret_cast<float*>(p.o) + attn_o_base(p, rr, b) + (int64_t)qrow * p.o_rs + (int64_t)h * D;
   for (int d = lane; d < D; d += 64) {
     float acc = 0.0f;
     for (int j = 0; j < kv_end; ++j) acc = fmaf(sc[w][j], vb[(int64_t)j * p.v_rs + d], acc);
@@ -1126,6 +1160,7 @@ __device__ __forceinline__ void attn_f32_body(const typename AttnParamsOf<RAGGED
 
 __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnParams p) { attn_f32_body<false>(p); }
 __global__ __launch_bounds__(256) void attn_f32_ragged_kernel(const AttnRaggedParams p) { attn_f32_body<true>(p); }
+__global__ __launch_bounds__(256) void attn_f32_segments_kernel(const AttnSegParams p) { attn_f32_body<true, true>(p); }
 
 // ---- exact fp32 path on the MATRIX cores (round 4): v_mfma_f32_32x32x2_f32, bit-equal to an fmaf chain per output --------------------
 // The one-wave-per-row kernel above re-reads the whole K and V of a head from L2 for every query row (181 KB per ViT row: ~12 GB per
@@ -1686,10 +1721,14 @@ extern "C" int stllm_attention(int dtype, const void* q, int64_t q_bs, int64_t q
 namespace {
 
 // RAGGED: a pad query row (every record of it is empty: 1 / ll would be infinite) is written as zeros.
-template <typename T, bool RAGGED = false>
-__global__ __launch_bounds__(64) void attn_ksplit_merge_kernel(const typename AttnParamsOf<RAGGED>::type p) {
+// SEG: a pad row of a segment does not exist in the packed buffer: nothing is written for it.
+template <typename T, bool RAGGED = false, bool SEG = false>
+__global__ __launch_bounds__(64) void attn_ksplit_merge_kernel(const typename AttnParamsOf<RAGGED, SEG>::type p) {
   const int lane = threadIdx.x, qrow = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
-  if constexpr (RAGGED) {
+  if constexpr (SEG) {
+    if (qrow >= seg_row(p, b).n) return;
+  }
+  if constexpr (RAGGED && !SEG) {
     if (qrow >= ragged_row(p, b).n) {
       *reinterpret_cast<uint32_t*>(p.o + ((int64_t)b * p.o_bs + (int64_t)qrow * p.o_rs + (int64_t)h * 128 + 2 * lane) * 2) = 0u;
       return;
@@ -1706,7 +1745,9 @@ __global__ __launch_bounds__(64) void attn_ksplit_merge_kernel(const typename At
     a1 = fmaf(rec[s * kSplRec + 2 * lane + 1], f, a1);
   }
   const float inv = 1.0f / ll;
-  uint32_t* op = reinterpret_cast<uint32_t*>(p.o + ((int64_t)b * p.o_bs + (int64_t)qrow * p.o_rs + (int64_t)h * 128 + 2 * lane) * 2);
+  uint32_t* op;
+  if constexpr (SEG) op = reinterpret_cast<uint32_t*>(p.o + ((int64_t)(seg_row(p, b).row0 + qrow) * p.o_rs + (int64_t)h * 128 + 2 * lane) * 2);
+  else op = reinterpret_cast<uint32_t*>(p.o + ((int64_t)b * p.o_bs + (int64_t)qrow * p.o_rs + (int64_t)h * 128 + 2 * lane) * 2);
   *op = Elem<T>::pack2(a0 * inv, a1 * inv);
 }
 
@@ -1730,24 +1771,24 @@ KsplitPlan ksplit_plan(int B, int H, int Sq, int Skv) {
   return pl;
 }
 
-template <typename T, int NW, bool RAGGED>
-void launch_ksplit_nw(const typename AttnParamsOf<RAGGED>::type& p, const KsplitPlan& pl, hipStream_t stream) {
-  hipLaunchKernelGGL((attn_mfma_kernel<T, 128, NW, true, RAGGED, RAGGED>), dim3(pl.chunks * pl.nsplit, p.H, p.B), dim3(64 * NW), 0, stream, p);
+template <typename T, int NW, bool RAGGED, bool SEG>
+void launch_ksplit_nw(const typename AttnParamsOf<RAGGED, SEG>::type& p, const KsplitPlan& pl, hipStream_t stream) {
+  hipLaunchKernelGGL((attn_mfma_kernel<T, 128, NW, true, RAGGED, RAGGED, SEG>), dim3(pl.chunks * pl.nsplit, p.H, p.B), dim3(64 * NW), 0, stream, p);
 }
 
-template <typename T, bool RAGGED = false>
-int launch_ksplit(typename AttnParamsOf<RAGGED>::type p, hipStream_t stream) {
+template <typename T, bool RAGGED = false, bool SEG = false>
+int launch_ksplit(typename AttnParamsOf<RAGGED, SEG>::type p, hipStream_t stream) {
   const KsplitPlan pl = ksplit_plan(p.B, p.H, p.Sq, p.Skv);
   p.nsplit = pl.nsplit;
   p.kps = pl.kps;
   switch (pl.nw) {
-    case 1: launch_ksplit_nw<T, 1, RAGGED>(p, pl, stream); break;
-    case 2: launch_ksplit_nw<T, 2, RAGGED>(p, pl, stream); break;
-    case 3: launch_ksplit_nw<T, 3, RAGGED>(p, pl, stream); break;
-    default: launch_ksplit_nw<T, 4, RAGGED>(p, pl, stream); break;
+    case 1: launch_ksplit_nw<T, 1, RAGGED, SEG>(p, pl, stream); break;
+    case 2: launch_ksplit_nw<T, 2, RAGGED, SEG>(p, pl, stream); break;
+    case 3: launch_ksplit_nw<T, 3, RAGGED, SEG>(p, pl, stream); break;
+    default: launch_ksplit_nw<T, 4, RAGGED, SEG>(p, pl, stream); break;
   }
-  hipLaunchKernelGGL((attn_ksplit_merge_kernel<T, RAGGED>), dim3(p.Sq, p.H, p.B), dim3(64), 0, stream, p);
-  STLLM_CHECK_LAUNCH(RAGGED ? "stllm_attention_offset_ragged(key split)" : "stllm_attention_offset(key split)");
+  hipLaunchKernelGGL((attn_ksplit_merge_kernel<T, RAGGED, SEG>), dim3(p.Sq, p.H, p.B), dim3(64), 0, stream, p);
+  STLLM_CHECK_LAUNCH(SEG ? "stllm_attention_segments(key split)" : RAGGED ? "stllm_attention_offset_ragged(key split)" : "stllm_attention_offset(key split)");
   stllm_set_last_kernel("attn_ksplit_kernel");
   return STLLM_OK;
 }
@@ -1800,6 +1841,24 @@ int dispatch_offset_ragged(const AttnRaggedParams& p, hipStream_t stream) {
   stllm_set_last_kernel("attn_mfma_kernel");
   const int nw = p.Sq <= 32 ? 1 : (p.Sq <= 64 ? 2 : 3);
   return nw == 1 ? launch_mfma_ragged<T, 1>(p, stream) : nw == 2 ? launch_mfma_ragged<T, 2>(p, stream) : launch_mfma_ragged<T, 3>(p, stream);
+}
+
+// stllm_attention_segments: dispatch_offset_ragged on the SEG instantiations — the same rule, plan and waves per workgroup at (R, H, max_n, max_kv).
+template <typename T, int NW>
+int launch_mfma_segments(const AttnSegParams& p, hipStream_t stream) {
+  dim3 grid((p.Sq + 32 * NW - 1) / (32 * NW), p.H, p.B), block(64 * NW);
+  hipLaunchKernelGGL((attn_mfma_kernel<T, 128, NW, false, true, true, true>), grid, block, 0, stream, p);
+  STLLM_CHECK_LAUNCH("stllm_attention_segments");
+  return STLLM_OK;
+}
+
+template <typename T>
+int dispatch_segments(const AttnSegParams& p, hipStream_t stream) {
+  const int opt = stllm_options().attn_ksplit;
+  if (p.ws && opt != 0 && (opt > 0 || ksplit_wins_ragged(p))) return launch_ksplit<T, true, true>(p, stream);
+  stllm_set_last_kernel("attn_mfma_kernel");
+  const int nw = p.Sq <= 32 ? 1 : (p.Sq <= 64 ? 2 : 3);
+  return nw == 1 ? launch_mfma_segments<T, 1>(p, stream) : nw == 2 ? launch_mfma_segments<T, 2>(p, stream) : launch_mfma_segments<T, 3>(p, stream);
 }
 
 }  // namespace
@@ -1890,6 +1949,52 @@ extern "C" int stllm_attention_offset_ragged(int dtype, const void* q, int64_t q
     return STLLM_OK;
   }
   return dtype == STLLM_BF16 ? dispatch_offset_ragged<bf16_t>(p, stream) : dispatch_offset_ragged<f16_t>(p, stream);
+}
+
+extern "C" int64_t stllm_attention_segments_workspace_bytes(int R, int H, int max_n, int max_kv) {
+  return stllm_attention_offset_workspace_bytes(R, H, max_n, max_kv);
+}
+
+// stllm_attention_offset_ragged on a PACKED query buffer: segment r = (slot[r], row0[r], q_off[r], kv_len[r]) reads the K / V of cache row slot[r] and owns the
+// packed rows row0[r] .. row0[r] + n_r - 1 of q and out (n_r = kv_len[r] - q_off[r] after ragged_row's clamps, at most max_n).  Schedule, plan and grid come
+// from (R, H, max_n, max_kv); the per-segment bounds and the table guard live in the kernels (seg_row).
+extern "C" int stllm_attention_segments(int dtype, const void* q, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v, int64_t v_bs,
+                                        int64_t v_rs, void* out, int64_t o_rs, int R, int H, int D, int T, int n_slots, int max_n, int max_kv, float scale,
+                                        const int32_t* slot, const int32_t* row0, const int32_t* q_off, const int32_t* kv_len, void* workspace,
+                                        int64_t workspace_bytes, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  STLLM_CHECK_ARG(q && k && v && out && slot && row0 && q_off && kv_len, "stllm_attention_segments: null pointer");
+  STLLM_CHECK_ARG(R > 0 && R <= 65535 && H > 0 && T > 0 && n_slots > 0 && max_n > 0 && max_kv > 0, "stllm_attention_segments: empty problem (or R > 65535)");
+  if (D != 128 || (dtype != STLLM_BF16 && dtype != STLLM_F16 && dtype != STLLM_F32)) {
+    stllm_set_error("stllm_attention_segments: head_dim %d / dtype %d unsupported (bf16 / fp16 / fp32 at head_dim 128)", D, dtype);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  if (dtype == STLLM_F32 && max_kv > kF32MaxKv) {
+    stllm_set_error("stllm_attention_segments: fp32 with max_kv %d > %d unsupported (the vector kernel keeps a row's scores in the LDS)", max_kv, kF32MaxKv);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  STLLM_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out), "stllm_attention_segments: pointers must be 16-byte aligned");
+  STLLM_CHECK_ARG(q_rs % 8 == 0 && k_rs % 8 == 0 && v_rs % 8 == 0 && o_rs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0,
+                  "stllm_attention_segments: strides must be multiples of 8 elements");
+  STLLM_CHECK_ARG(((reinterpret_cast<uintptr_t>(slot) | reinterpret_cast<uintptr_t>(row0) | reinterpret_cast<uintptr_t>(q_off) |
+                    reinterpret_cast<uintptr_t>(kv_len)) & 3) == 0, "stllm_attention_segments: tables must be 4-byte aligned");
+  AttnSegParams p{};
+  p.q = (const char*)q; p.q_bs = 0; p.q_rs = q_rs;
+  p.k = (const char*)k; p.k_bs = k_bs; p.k_rs = k_rs;
+  p.v = (const char*)v; p.v_bs = v_bs; p.v_rs = v_rs;
+  p.o = (char*)out; p.o_bs = 0; p.o_rs = o_rs;
+  p.B = R; p.H = H; p.Sq = max_n; p.Skv = max_kv; p.D = D;
+  p.scale = scale; p.scale_log2 = scale * 1.44269504088896340736f;
+  p.causal = 1; p.kv_len = kv_len; p.q_off_tab = q_off;
+  p.slot = slot; p.row0 = row0; p.T = T; p.n_slots = n_slots;
+  if (workspace && aligned16(workspace) && workspace_bytes >= stllm_attention_segments_workspace_bytes(R, H, max_n, max_kv)) p.ws = reinterpret_cast<float*>(workspace);
+  if (dtype == STLLM_F32) {
+    stllm_set_last_kernel("attn_f32_kernel");
+    hipLaunchKernelGGL(attn_f32_segments_kernel, dim3((max_n + 3) / 4, H, R), dim3(256), 0, stream, p);
+    STLLM_CHECK_LAUNCH("stllm_attention_segments(fp32)");
+    return STLLM_OK;
+  }
+  return dtype == STLLM_BF16 ? dispatch_segments<bf16_t>(p, stream) : dispatch_segments<f16_t>(p, stream);
 }
 
 extern "C" int64_t stllm_attention_decode_workspace_bytes(int B, int H, int Skv) {

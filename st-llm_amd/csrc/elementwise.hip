@@ -139,6 +139,23 @@ __global__ __launch_bounds__(256) void kv_append_spans_kernel(const char* __rest
   reinterpret_cast<uint4*>(cache + (int64_t)b * batch_stride + ps * row_stride + col0_bytes)[c] = v;
 }
 
+// kv_append_spans_kernel for a PACKED source (stllm_kv_append_segments): the [k | v] bytes of packed row row0[r] + i -> cache row slot[r] at position
+// pos0[r] + i, for i < n[r]; blockIdx.z = segment r, blockIdx.y = i.  A segment whose slot is outside [0, n_slots) or whose packed rows are outside [0, T)
+// writes nothing (the table guard of stllm_attention_segments), as do positions outside [0, max_len).
+__global__ __launch_bounds__(256) void kv_append_segments_kernel(const char* __restrict__ src, int64_t src_stride, char* __restrict__ cache,
+                                                                 int64_t batch_stride, int64_t row_stride, const int32_t* __restrict__ slot,
+                                                                 const int32_t* __restrict__ row0, const int32_t* __restrict__ pos0,
+                                                                 const int32_t* __restrict__ n, int T, int n_slots, int max_len, int col0_bytes, int n16) {
+  const int r = blockIdx.z, i = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+  const int nr = n[r], sl = slot[r], r0 = row0[r];
+  if (c >= n16 || i >= nr) return;
+  if (sl < 0 || sl >= n_slots || r0 < 0 || (int64_t)r0 + nr > T) return;
+  const int64_t ps = (int64_t)pos0[r] + i;
+  if (ps < 0 || ps >= max_len) return;
+  const uint4 v = reinterpret_cast<const uint4*>(src + (int64_t)(r0 + i) * src_stride + col0_bytes)[c];
+  reinterpret_cast<uint4*>(cache + (int64_t)sl * batch_stride + ps * row_stride + col0_bytes)[c] = v;
+}
+
 // ---- token selection: stllm_select_tokens / stllm_beam_candidates (include/stllm_hip.h) --------------------------------------------------------------
 // One workgroup per row; the row lives in the LDS as fp32 from the staging on (V <= ~40 k floats), every later pass reads the LDS.  Reductions: a
 // per-thread partial in index order, the xor butterfly inside a wave, the four wave results combined in a fixed order — no atomics, so a launch is
@@ -462,6 +479,33 @@ extern "C" int stllm_kv_append_spans(int dtype, const void* src, int64_t ld_src,
                      reinterpret_cast<const char*>(src), ld_src * e, reinterpret_cast<char*>(cache), batch_stride * e, row_stride * e, pos0, n, S, max_len, col0,
                      n16);
   STLLM_CHECK_LAUNCH("stllm_kv_append_spans");
+  return STLLM_OK;
+}
+
+extern "C" int stllm_kv_append_segments(int dtype, const void* src, int64_t ld_src, void* cache, int64_t batch_stride, int64_t row_stride,
+                                        const int32_t* slot, const int32_t* row0, const int32_t* pos0, const int32_t* n, int R, int T, int n_slots,
+                                        int max_n, int hidden, int max_len, void* stream) {
+  STLLM_CHECK_ARG(src && cache && slot && row0 && pos0 && n, "stllm_kv_append_segments: null pointer");
+  STLLM_CHECK_ARG(R > 0 && R <= 65535 && T > 0 && n_slots > 0 && max_n > 0 && max_n <= 65535 && hidden > 0 && max_len > 0,
+                  "stllm_kv_append_segments: bad R=%d T=%d n_slots=%d max_n=%d hidden=%d max_len=%d (R, max_n <= 65535)", R, T, n_slots, max_n, hidden, max_len);
+  int e;
+  switch (dtype) {
+    case STLLM_BF16: case STLLM_F16: e = 2; break;
+    case STLLM_F32: e = 4; break;
+    default: stllm_set_error("stllm_kv_append_segments: bad dtype %d", dtype); return STLLM_ERR_BAD_DTYPE;
+  }
+  STLLM_CHECK_ARG(ld_src >= 3 * (int64_t)hidden && row_stride >= 3 * (int64_t)hidden && batch_stride >= (int64_t)max_len * row_stride,
+                  "stllm_kv_append_segments: rows of 3 * hidden elements, max_len rows per cache row");
+  STLLM_CHECK_ARG(((int64_t)hidden * e) % 16 == 0 && (ld_src * e) % 16 == 0 && (row_stride * e) % 16 == 0 && (batch_stride * e) % 16 == 0 &&
+                      aligned16(src) && aligned16(cache) &&
+                      ((reinterpret_cast<uintptr_t>(slot) | reinterpret_cast<uintptr_t>(row0) | reinterpret_cast<uintptr_t>(pos0) |
+                        reinterpret_cast<uintptr_t>(n)) & 3) == 0,
+                  "stllm_kv_append_segments: 16-byte vector copies need 16-byte aligned pointers, strides and hidden");
+  const int col0 = hidden * e, n16 = (2 * hidden * e) / 16;
+  hipLaunchKernelGGL(kv_append_segments_kernel, dim3((n16 + 255) / 256, max_n, R), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<const char*>(src), ld_src * e, reinterpret_cast<char*>(cache), batch_stride * e, row_stride * e, slot, row0, pos0, n, T,
+                     n_slots, max_len, col0, n16);
+  STLLM_CHECK_LAUNCH("stllm_kv_append_segments");
   return STLLM_OK;
 }
 

@@ -30,7 +30,8 @@ EXPORTS = ["stllm_last_error", "stllm_abi_version", "stllm_last_kernel", "stllm_
            "stllm_attention_offset_workspace_bytes", "stllm_attention_offset", "stllm_llama_layers_extend", "stllm_gemv_w8", "stllm_gemv_q4",
            "stllm_attention_decode_ragged_workspace_bytes", "stllm_attention_decode_ragged", "stllm_kv_append_rows",
            "stllm_attention_shared_workspace_bytes", "stllm_attention_shared", "stllm_select_tokens", "stllm_beam_candidates",
-           "stllm_attention_offset_ragged_workspace_bytes", "stllm_attention_offset_ragged", "stllm_kv_append_spans"]
+           "stllm_attention_offset_ragged_workspace_bytes", "stllm_attention_offset_ragged", "stllm_kv_append_spans",
+           "stllm_attention_segments_workspace_bytes", "stllm_attention_segments", "stllm_kv_append_segments"]
 
 
 def torch_dtype(d):
@@ -207,6 +208,10 @@ def _bind(L, strict=True):
     B("stllm_attention_offset_ragged_workspace_bytes", [c_int] * 4, c_int64)
     B("stllm_attention_offset_ragged", [c_int] + [c_void_p, c_int64, c_int64] * 4 + [c_int] * 5 + [c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
     B("stllm_kv_append_spans", [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p])
+    B("stllm_attention_segments_workspace_bytes", [c_int] * 4, c_int64)
+    B("stllm_attention_segments", [c_int, c_void_p, c_int64] + [c_void_p, c_int64, c_int64] * 2 + [c_void_p, c_int64] + [c_int] * 7 + [c_float] + [c_void_p] * 5 +
+      [c_int64, c_void_p])
+    B("stllm_kv_append_segments", [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64] + [c_void_p] * 4 + [c_int] * 6 + [c_void_p])
     B("stllm_attention_offset", [c_int] + [c_void_p, c_int64, c_int64] * 4 + [c_int] * 5 + [c_float, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_llama_layers_extend", [ctypes.POINTER(LlamaLayersArgs), ctypes.POINTER(LlamaLayerWeights), c_int, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_gemv_w8", [ctypes.POINTER(GemvW8Args), c_void_p])
@@ -1079,6 +1084,37 @@ def attention_offset_ragged(q, k, v, q_off, kv_len, *, B, H, Sq, max_kv, D, scal
     return out
 
 
+def segments_available(device):
+    """attention_segments and kv_append_segments can serve tensors on `device`: a device check, nothing more (as ragged_extend_available).
+    LlamaModel.step_segments asks before anything is written; a stand-in for this module that states the two contracts answers for itself."""
+    return torch.device(device).type == "cuda"
+
+
+def attention_segments(q, k, v, slot, row0, q_off, kv_len, *, H, D, T, n_slots, max_n, max_kv, scale, out=None, k_strides=None, v_strides=None):
+    """stllm_attention_segments: causal attention for R segments of a PACKED query buffer.  q: 2-D view of T packed rows (row stride q.stride(0)); k / v: 2-D
+    views of a cache of n_slots rows with (cache row, position) strides in elements; slot, row0, q_off, kv_len: int32 [R] on the device — segment r reads
+    cache row slot[r], owns the packed rows row0[r] .. row0[r] + n_r - 1 (n_r = kv_len[r] - q_off[r] <= max_n) and sits behind q_off[r] cached positions;
+    max_kv is the host-known bound of kv_len.  Only the packed rows of the segments are written (out: [T, H * D]); a segment whose tables point outside
+    the buffers does nothing.  bf16 / fp16 / fp32 at D = 128 (fp32: max_kv <= 2048); anything else is an error (STLLM_ERR_UNSUPPORTED), not a fallback."""
+    td = q.dtype
+    R = slot.numel()
+    for t, what in ((slot, "slot"), (row0, "row0"), (q_off, "q_off"), (kv_len, "kv_len")):
+        _req(t, torch.int32, what)
+        if t.numel() != R:
+            raise RuntimeError(f"attention_segments: {what} has {t.numel()} entries for R = {R}")
+    if q.shape[0] < T or (out is not None and out.shape[0] < T):
+        raise RuntimeError(f"attention_segments: q {tuple(q.shape)} / out {None if out is None else tuple(out.shape)} hold fewer than T = {T} rows")
+    ks = k_strides if k_strides is not None else (max_kv * k.stride(0), k.stride(0))
+    vs = v_strides if v_strides is not None else (max_kv * v.stride(0), v.stride(0))
+    if out is None:
+        out = torch.empty((T, H * D), device=q.device, dtype=td)
+    ws = attention_offset_workspace(R, H, max_n, max_kv, q.device) if td != torch.float32 and D == 128 else None
+    _check(lib().stllm_attention_segments(dtype_code(td), _p(q), q.stride(0), _p(k), ks[0], ks[1], _p(v), vs[0], vs[1], _p(out), out.stride(0),
+                                          R, H, D, T, n_slots, max_n, max_kv, scale, _p(slot), _p(row0), _p(q_off), _p(kv_len),
+                                          _p(ws), ws.numel() if ws is not None else 0, _stream()), "stllm_attention_segments")
+    return out
+
+
 def attention_shared(q, kp, vp, ks, vs, *, B, G, H, Sq, P, D, scale, max_sfx, sfx_len=None, sfx_q_off=0, causal=False, out=None,
                      q_strides=None, kp_strides=None, ks_strides=None):
     """stllm_attention_shared: B = G * R query rows, the R rows of group g read the P keys of prefix row g ONCE (kp / vp: 2-D views of the prefix buffer,
@@ -1129,6 +1165,24 @@ def kv_append_spans(src, cache, pos0, n, *, S):
         raise RuntimeError(f"kv_append_spans: src {tuple(src.shape)}, cache {tuple(cache.shape)}, pos0 {tuple(pos0.shape)}, n {tuple(n.shape)}, S {S}")
     _check(lib().stllm_kv_append_spans(dtype_code(cache.dtype), _p(src), src.stride(0), _p(cache), cache.stride(0), cache.stride(1), _p(pos0), _p(n), B, S,
                                        D3 // 3, max_len, _stream()), "stllm_kv_append_spans")
+    return cache
+
+
+def kv_append_segments(src, cache, slot, row0, pos0, n, *, T, max_n):
+    """stllm_kv_append_segments: cache[slot[r], pos0[r] + i, cols] = src[row0[r] + i, cols] for i < n[r] (<= max_n) and the [k | v] columns of the packed
+    fused rows src [>= T, 3*hidden]; cache: [n_slots, max_len, 3*hidden]; slot, row0, pos0, n: int32 [R] on the device.  Segments whose tables point outside
+    the buffers and positions outside [0, max_len) write nothing.  All compute dtypes."""
+    _req(src, cache.dtype, "src")
+    R = slot.numel()
+    for t, what in ((slot, "slot"), (row0, "row0"), (pos0, "pos0"), (n, "n")):
+        _req(t, torch.int32, what)
+        if t.numel() != R:
+            raise RuntimeError(f"kv_append_segments: {what} has {t.numel()} entries for R = {R}")
+    n_slots, max_len, D3 = cache.shape
+    if src.dim() != 2 or src.shape[0] < T or src.shape[1] != D3 or cache.stride(2) != 1 or src.stride(1) != 1:
+        raise RuntimeError(f"kv_append_segments: src {tuple(src.shape)}, cache {tuple(cache.shape)}, T {T}")
+    _check(lib().stllm_kv_append_segments(dtype_code(cache.dtype), _p(src), src.stride(0), _p(cache), cache.stride(0), cache.stride(1), _p(slot), _p(row0),
+                                          _p(pos0), _p(n), R, T, n_slots, max_n, D3 // 3, max_len, _stream()), "stllm_kv_append_segments")
     return cache
 
 

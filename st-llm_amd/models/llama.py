@@ -231,6 +231,35 @@ class KVCache:
         assert self.len > 0 and max_new is not None and max_new > 0, "KVCache.share: a non-empty base and room for new positions (max_new=)"
         return KVCache(len(self.qkv), rows, self.len + max_new, self.hidden, self.qkv[0].dtype, self.qkv[0].device, base=self)
 
+    def row_lens(self):
+        """the length of every row as a list (a uniform cache: `len`, `batch` times)"""
+        return list(self.lens) if self.lens is not None else [self.len] * self.batch
+
+    def load_row(self, slot, src, src_row=0):
+        """copy the src.len positions of row `src_row` of a UNIFORM cache without a base (a prefilled video prefix) into row `slot` of this one — the
+        [k | v] columns of every layer — and set that row's length; every other row keeps its length and its bytes.  `src` is only read."""
+        if src.base is not None:
+            raise NotImplementedError("KVCache.load_row: the source has a shared base; fork() it first")
+        if self.base is not None:
+            raise NotImplementedError("KVCache.load_row: a cache with a shared base holds no whole rows to load into")
+        if src.lens is not None:
+            raise NotImplementedError("KVCache.load_row: the source must be uniform (rows of one length)")
+        n, D = src.len, self.hidden
+        assert 0 <= slot < self.batch and 0 <= src_row < src.batch and n <= self.max_len and len(src.qkv) == len(self.qkv) and src.hidden == D
+        assert src.qkv[0].dtype == self.qkv[0].dtype
+        for dst, s in zip(self.qkv, src.qkv):
+            dst[slot, :n, D:].copy_(s[src_row, :n, D:])
+        lens = self.row_lens()
+        lens[slot] = n
+        self.set_lens(lens)
+
+    def release(self, slot):
+        """row `slot` holds nothing any more (its bytes are don't-care from here on); every other row is left alone"""
+        assert 0 <= slot < self.batch and self.base is None
+        lens = self.row_lens()
+        lens[slot] = 0
+        self.truncate(lens)
+
     def truncate(self, n):
         """forget the positions from n on (their rows are simply overwritten by the next extend / decode_step).  n: an int for every row, or a list with
         one length per row (each at most what the row holds).  A cache with a base keeps at least the base's positions."""
@@ -538,6 +567,66 @@ class LlamaModel(nn.Module):
         cache.set_lens([p + n for p, n in zip(have, new)])
         h16, h32 = hip.rmsnorm(x, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
         return h32.view(B, S, D), h16
+
+    def step_segments(self, embeds, cache, segments):
+        """One pass through the decoder layers over a PACKED step: embeds f32 [T, D] is the concatenation of the segments' tokens,
+        segments a list of (slot, n) in packed order — n >= 1 tokens appended behind the cache.lens[slot] positions that row `slot` of `cache` holds (one
+        token for a running request, a whole prompt for a newly admitted one; slots distinct).  Per layer: RMSNorm -> QKV GEMM + RoPE into a dense [T, 3D]
+        scratch (RoPE rows gathered at lens[slot] + i, rope_seq = T) -> hip.kv_append_segments -> hip.attention_segments -> o_proj -> MLP.  No pad rows
+        anywhere: T GEMM rows, T query rows.  Sets the length of every named slot to lens + n; a slot that is not named keeps its length and its bytes.
+        Returns the final-norm hidden rows of every segment's LAST token only: (f32 [R, D], compute dtype [R, D]).  bf16 / fp16 / fp32; the split
+        modes, a cache with a base and quantised decode weights raise (the quantised modes serve pure-decode steps through decode_step)."""
+        cfg = self.config
+        dt = runtime.compute_dtype()
+        if runtime.gemm_split():
+            raise NotImplementedError("LlamaModel.step_segments runs in the bf16 / fp16 / fp32 modes; the bf16x3 / mixed modes have no segment path")
+        if runtime.decode_weights() is not None:
+            raise NotImplementedError(f"LlamaModel.step_segments streams the 16-bit weights: {runtime.decode_weights()} decode weights serve decode_step only")
+        if cache.base is not None:
+            raise NotImplementedError("LlamaModel.step_segments on a KV cache with a shared base: fork() it first")
+        T, D = embeds.shape
+        H = cfg.num_attention_heads
+        hd = D // H
+        dev = embeds.device
+        if not hip.segments_available(dev):
+            raise NotImplementedError("LlamaModel.step_segments needs hip.attention_segments / hip.kv_append_segments, which this backend does not provide for " +
+                                      str(dev))
+        segments = [(int(s), int(n)) for s, n in segments]
+        slots, new = [s for s, _ in segments], [n for _, n in segments]
+        assert segments and len(set(slots)) == len(slots) and all(0 <= s < cache.batch for s in slots), "step_segments: slots must be distinct and in range"
+        assert min(new) >= 1 and sum(new) == T, "step_segments: every segment carries at least one token and the segments cover the packed rows"
+        assert cache.qkv[0].dtype == dt
+        lens = cache.row_lens()
+        have = [lens[s] for s in slots]
+        assert all(p + n <= cache.max_len for p, n in zip(have, new)), "KV cache full"
+        row0 = [sum(new[:r]) for r in range(len(new))]
+        layers = self.pack(dt)
+        x = embeds.float().clone()
+        cos, sin = self.rope(cache.max_len, dev)
+
+        def tab(v):
+            return hip.h2d(torch.tensor(v, dtype=torch.int32), dev)
+        pos = tab([p + i for p, n in zip(have, new) for i in range(n)])
+        cos, sin = hip.gather_rows(cos, pos), hip.gather_rows(sin, pos)
+        slot_t, row0_t, q_off, n_new, kv_len = tab(slots), tab(row0), tab(have), tab(new), tab([p + n for p, n in zip(have, new)])
+        max_n, max_kv = max(new), max(p + n for p, n in zip(have, new))
+        dense = torch.empty((T, 3 * D), device=dev, dtype=dt)
+        strides = cache.kv(0)[2]
+
+        def attn(li, dense):
+            hip.kv_append_segments(dense, cache.qkv[li], slot_t, row0_t, q_off, n_new, T=T, max_n=max_n)
+            k, v, _ = cache.kv(li)
+            return hip.attention_segments(dense[:, :D], k, v, slot_t, row0_t, q_off, kv_len, H=H, D=hd, T=T, n_slots=cache.batch, max_n=max_n, max_kv=max_kv,
+                                          scale=hd ** -0.5, k_strides=strides, v_strides=strides)
+        proj = gemm_proj(layers, dt, True)
+        for li, pk in enumerate(layers):
+            decoder_layer(self, dt, x, pk, li, proj=proj, qkv_to=lambda li: {"out": dense}, attn=attn, rope=(cos, sin), rope_seq=T)
+        for s, p, n in zip(slots, have, new):
+            lens[s] = p + n
+        cache.set_lens(lens)
+        last = hip.gather_rows(x, tab([r0 + n - 1 for r0, n in zip(row0, new)]))
+        h16, h32 = hip.rmsnorm(last, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
+        return h32, h16
 
     def extend_layers_shared(self, x, layers, B, S, pos, cos, sin, cache, dt, lengths=None):
         """extend's layer loop for a cache with a shared base (KVCache.share): the S new rows sit at the local positions [off, off + S), off = pos - base_len,

@@ -172,6 +172,74 @@ if "--ragged-suffix" in sys.argv:
         print(f"ragged suffix B={B} P={','.join(map(str, Ps))} n={','.join(map(str, ns))}: key-split {fmt('split')}  tile {fmt('tile')}  auto {fmt('auto')} -> {auto}"
               f"  | parent: per-row offset calls {fmt('per-row')}  {S} decode steps {fmt('steps')}", flush=True)
     sys.exit(0)
+if "--segments" in sys.argv:
+    # --segments [P1,P2,...:n1,n2,...] (repeatable; default: 15 one-token segments behind 560 .. 1100 positions plus one 40-token segment behind 580): the packed
+    # admission step of serving.Engine — segment r appends n_r rows behind P_r cached positions of its own slot.
+    #   segments : hip.attention_segments on the packed [T, 3 H D] scratch, key split forced on (1), forced off (0) and by the rule (auto);
+    #   padded   : what the parent commit has — hip.attention_offset_ragged on the padded R x max(n) layout (auto) ...
+    #   dec+off  : ... or the ragged decode attention for the one-token rows plus one stllm_attention_offset call per longer row.
+    # Same process and buffers, alternating, every timing a captured graph of 20 calls; best of 5 replays, every round printed.
+    def timed_q(fn, rounds=5):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(20):
+                fn()
+        g.replay(); torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        best = float("inf")
+        for _ in range(rounds):
+            s.record(); g.replay(); e.record(); torch.cuda.synchronize()
+            best = min(best, s.elapsed_time(e) / 20 * 1e3)
+        return best
+    H, D, dt = 32, 128, torch.bfloat16
+    HD, W = H * D, 3 * H * D
+    specs = [sys.argv[i + 1] for i, a in enumerate(sys.argv) if a == "--segments" and i + 1 < len(sys.argv) and ":" in sys.argv[i + 1]]
+    default = ",".join(str(560 + (540 * i) // 14) for i in range(15)) + ",580:" + ",".join(["1"] * 15) + ",40"
+    for spec in specs or [default]:
+        Ps, ns = (list(map(int, part.split(","))) for part in spec.split(":"))
+        assert len(Ps) == len(ns) and min(ns) >= 1
+        R, S, T, max_kv = len(Ps), max(ns), sum(ns), max(p + n for p, n in zip(Ps, ns))
+        ML = max_kv + 8
+        buf = torch.randn(R * ML, W, device="cuda").to(dt)
+        packed = torch.randn(T, W, device="cuda").to(dt)
+        padded = torch.randn(R * S, W, device="cuda").to(dt)
+        st = (ML * W, W)
+        out, out_p = torch.empty(T, HD, device="cuda", dtype=dt), torch.empty(R * S, HD, device="cuda", dtype=dt)
+        i32 = lambda x: torch.tensor(x, dtype=torch.int32).cuda()
+        row0 = [sum(ns[:r]) for r in range(R)]
+        slot, row0_t, q_off, kv_len = i32(list(range(R))), i32(row0), i32(Ps), i32([p + n for p, n in zip(Ps, ns)])
+        ones = [r for r in range(R) if ns[r] == 1]
+        dec_len = i32([Ps[r] + 1 for r in ones]) if ones else None
+        seg = lambda: hip.attention_segments(packed[:, :HD], buf[:, HD:2 * HD], buf[:, 2 * HD:], slot, row0_t, q_off, kv_len, H=H, D=D, T=T, n_slots=R, max_n=S,
+                                             max_kv=max_kv, scale=D ** -0.5, out=out, k_strides=st, v_strides=st)
+        pad = lambda: hip.attention_offset_ragged(padded[:, :HD], buf[:, HD:2 * HD], buf[:, 2 * HD:], q_off, kv_len, B=R, H=H, Sq=S, max_kv=max_kv, D=D,
+                                                  scale=D ** -0.5, out=out_p, q_strides=(S * W, W), k_strides=st, v_strides=st)
+
+        def dec_off():   # (the one-token rows are taken as the first len(ones) cache rows: the same keys are walked)
+            if ones:
+                hip.attention(packed[:, :HD], buf[:, HD:2 * HD], buf[:, 2 * HD:], B=len(ones), H=H, Sq=1, Skv=max(Ps[r] + 1 for r in ones), D=D, scale=D ** -0.5,
+                              kv_len=dec_len, q_strides=(W, W), k_strides=st, v_strides=st, out=out[:len(ones)])
+            for r in range(R):
+                if ns[r] > 1:
+                    hip.attention(packed[row0[r]:, :HD], buf[r * ML:, HD:2 * HD], buf[r * ML:, 2 * HD:], B=1, H=H, Sq=ns[r], Skv=Ps[r] + ns[r], D=D, scale=D ** -0.5,
+                                  causal=True, q_strides=(ns[r] * W, W), k_strides=st, v_strides=st, q_off=Ps[r], out=out[row0[r]:row0[r] + ns[r]])
+        res = {}
+        try:
+            for rnd in range(2):
+                for name, opt, f in (("split", 1, seg), ("tile", 0, seg), ("auto", -1, seg), ("padded", -1, pad), ("dec+off", -1, dec_off)):
+                    hip.set_option("attn_ksplit", opt)
+                    res.setdefault(name, []).append(timed_q(f))
+        finally:
+            hip.set_option("attn_ksplit", -1)
+        seg()
+        auto = hip.lib().stllm_last_kernel().decode()
+        fmt = lambda n: f"{min(res[n]):7.1f} us (" + " ".join(f"{x:.1f}" for x in res[n]) + ")"
+        print(f"segments R={R} T={T} P={','.join(map(str, Ps))} n={','.join(map(str, ns))}: key-split {fmt('split')}  tile {fmt('tile')}  auto {fmt('auto')} -> {auto}"
+              f"  | parent: padded {R}x{S} ragged {fmt('padded')}  decode + offset calls {fmt('dec+off')}", flush=True)
+    sys.exit(0)
 if "--suffix" in sys.argv:
     # LlamaModel.extend's shape: Sq new rows behind q_off cached ones, operands addressed inside one fused cache buffer as the model passes them.
     # The offset tile kernel (attn_ksplit = 0) and the key-split pair (1) on the same buffers, same process, alternating; "auto" is the dispatch rule.

@@ -30,6 +30,10 @@ ap.add_argument("--sample", action="store_true", help="with --generate: top-p sa
 ap.add_argument("--cases", default="", help="with --generate: several workloads in one process (one model build), e.g. g1,g5,g16,s1,s16,b5 — g / s = greedy / sampled "
                                             "rows, b = beams of one prompt; default: the one case --rows / --sample / --beams describe")
 ap.add_argument("--sync-every", type=int, default=1, help="with --generate, selection 'device': generate(sync_every=K)")
+ap.add_argument("--serve", default="", help="N,K: N questions behind one prefilled --prefix-len prefix through K slots of serving.Engine (continuous batching) against "
+                                            "generate(batching='ragged') in waves of K; mixed answer lengths (printed), EOS disabled, useful tokens/s of both")
+ap.add_argument("--admit", default="", help="R,n: the whole admission step — R running rows behind 560 .. 1100 positions plus one admitted n-token row: "
+                                            "LlamaModel.step_segments against extend(lengths=[0] * R + [n]) followed by a decode_step, alternating")
 ap.add_argument("--prefix-len", type=int, default=576, help="positions of the shared prefix of --share-prefix")
 args = ap.parse_args()
 torch.set_grad_enabled(False)
@@ -213,6 +217,105 @@ def generate_e2e(n_new, R, nb, sample):
         print(f"selection step alone ({what}, V {V}, n_prev {n_prev}) [{name}]: {sorted(us)[1]:.1f} us (blocks {' '.join(f'{x:.1f}' for x in us)})", flush=True)
 
 
+SERVE_LENGTHS = [16, 96, 32, 64, 24, 128, 48, 8]   # answer lengths of --serve, cycled over the N questions
+
+
+def serve_e2e(N, K):
+    """useful tokens/s: Engine (a slot is refilled the step after its answer ends) vs waves of K questions, each wave one ragged generate() that lasts as long as
+    its longest answer (what the rows that finished earlier cost while they are fed pad tokens).  Alternating, 3 runs each, the first warms up."""
+    from stllm_amd import serving
+    P = args.prefix_len
+    video = torch.randn(1, P, 4096, device=dev) * 0.02
+    prefix = lm.new_cache(1, P, dev)
+    lm.prefill(video, None, cache=prefix)
+    qlens = [9 + (5 * i) % 17 for i in range(N)]
+    alens = [SERVE_LENGTHS[i % len(SERVE_LENGTHS)] for i in range(N)]
+    qs = [torch.randn(n, 4096, device=dev) * 0.02 for n in qlens]
+
+    def engine():
+        eng = serving.Engine(model, K, P + max(qlens) + max(alens), eos_token_id=None, repetition_penalty=1.5)
+        for q, n in zip(qs, alens):
+            eng.submit(q, prefix=prefix, max_new_tokens=n)
+        out = eng.run()
+        assert sorted(ids.numel() for _, ids in out) == sorted(alens)
+        return eng.steps
+
+    def waves():
+        for w in range(0, N, K):
+            rows, n_new = qs[w:w + K], max(alens[w:w + K])
+            emb = torch.zeros(len(rows), max(q.shape[0] for q in rows), 4096, device=dev)
+            mask = torch.zeros(emb.shape[:2], dtype=torch.long)
+            for i, q in enumerate(rows):
+                emb[i, :q.shape[0]] = q
+                mask[i, :q.shape[0]] = 1
+            model.generate(inputs_embeds=emb, attention_mask=mask, batching="ragged", prefix_cache=prefix, max_new_tokens=n_new, eos_token_id=None,
+                           repetition_penalty=1.5)
+    res, steps = {}, None
+    for name, f in (("engine", engine), ("waves", waves)) * 3:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = f()
+        torch.cuda.synchronize()
+        res.setdefault(name, []).append(time.perf_counter() - t0)
+        steps = r if name == "engine" else steps
+    wave_steps = sum(max(alens[w:w + K]) for w in range(0, N, K))
+    for name, ts in res.items():
+        t = min(ts[1:])
+        extra = f"{steps['segments']} admission + {steps['decode']} decode steps" if name == "engine" else f"{wave_steps} decode steps in {-(-N // K)} waves"
+        print(f"{N} questions over {K} slots behind a {P}-token prefix, answers {','.join(map(str, alens))} ({sum(alens)} tokens), weights {args.weights} [{name}]: "
+              f"{t * 1e3:.1f} ms = {sum(alens) / t:.1f} useful tok/s, {extra} (runs {' '.join(f'{x * 1e3:.1f}' for x in ts)})", flush=True)
+
+
+def admit_step(R, n):
+    """ms of one admission step, alternating blocks of --tokens steps, 5 blocks each, medians; every step is undone (truncate)"""
+    lens = [560 + (540 * i) // max(R - 1, 1) for i in range(R)]
+    L = max(lens) + n + 8
+    c = lm.new_cache(R + 1, L, dev)
+    lm.prefill(torch.randn(R + 1, max(lens), 4096, device=dev) * 0.02, None, cache=c)
+    keep = lens + [0]
+    c.truncate(keep)
+    tok = torch.randn(R, 4096, device=dev) * 0.02
+    new = torch.randn(n, 4096, device=dev) * 0.02
+    packed = torch.cat([tok, new])
+    pad = torch.zeros(R + 1, n, 4096, device=dev)
+    pad[R] = new
+    tok16 = torch.randn(R + 1, 1, 4096, device=dev) * 0.02
+
+    def seg():
+        _, h = lm.step_segments(packed, c, [(r, 1) for r in range(R)] + [(R, n)])
+        model.logits_from(h, R + 1, 1)
+        c.truncate(keep)
+
+    def parent():
+        lm.extend(pad, c, lengths=[0] * R + [n])
+        _, h = lm.decode_step(tok16, c)
+        model.logits_from(h, R + 1, 1)
+        c.truncate(keep)
+
+    def block(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.tokens):
+            f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.tokens * 1e3
+    for _ in range(2):
+        block(seg), block(parent)
+    ts, tp = [], []
+    for _ in range(5):
+        ts.append(block(seg))
+        tp.append(block(parent))
+    print(f"admission step ({R} running rows behind {lens[0]} .. {lens[-1]} positions + one {n}-token row): step_segments {sorted(ts)[2]:.3f} ms "
+          f"(blocks {' '.join(f'{x:.3f}' for x in ts)}), extend(n_b = 0 for the running rows) + decode_step {sorted(tp)[2]:.3f} ms (blocks {' '.join(f'{x:.3f}' for x in tp)})"
+          f" — the parent pair also decodes the admitted row's first token", flush=True)
+
+
+if args.serve:
+    serve_e2e(*[int(x) for x in args.serve.split(",")])
+    sys.exit(0)
+if args.admit:
+    admit_step(*[int(x) for x in args.admit.split(",")])
+    sys.exit(0)
 if args.generate:
     cases = args.cases.split(",") if args.cases else [f"b{args.beams}" if args.beams else f"{'s' if args.sample else 'g'}{args.rows}"]
     for c in cases:
