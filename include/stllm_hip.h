@@ -523,13 +523,16 @@ int stllm_rmsnorm(int dtype, const float* x, int64_t ldx, const float* gamma, fl
  *         Qformer.py:785-801 with -10000 == exact 0 after fp32 softmax).
  * causal: key j visible to query i iff j <= i (Sq == Skv).
  * D in {64, 88, 128}; all strides multiples of 8 elements; pointers 16-byte aligned.
- * Memory regions.  Never read: q rows >= Sq and K / V rows >= Skv of a batch entry (a key tile overhanging Skv is filled with zeros in the LDS, not
- * loaded), columns behind H * D.  READ, WEIGHTLESS, MUST BE FINITE: the K / V rows in [kv_len[b], Skv).  The tile kernels load whole key tiles up to Skv
+ * Memory regions.  Never read: q rows >= Sq and K / V rows >= Skv of a batch entry (the part of a key tile that overhangs Skv is never loaded: the
+ * register-staged kernels put zeros into the LDS there, the LDS-DMA kernels a second copy of row Skv - 1, its scores masked), columns behind H * D.  READ, WEIGHTLESS, MUST BE FINITE: the K / V rows in [kv_len[b], Skv).  The tile kernels load whole key tiles up to Skv
  * and mask the SCORES; a masked probability is an exact 0, and 0 x NaN in V would reach the output — so the caller must have written finite values there
  * (the prefill does: they are the projections of the pad positions).  Memory that may be uninitialised behind a length belongs behind Skv, or to
  * stllm_attention_decode_ragged / stllm_attention_shared, which bound their loads by the length.  (The fp32 one-wave-per-row vector kernel bounds its key loop by
  * kv_len; the fp32 matrix-core kernel loads up to Skv like the 16-bit ones: callers must not rely on which kernel runs.)  Query rows at or behind kv_len[b] of a causal call are ordinary rows: read, and their
  * outputs written (they attend the valid keys).  Never written: out behind H * D columns of a row, rows >= Sq of a batch entry.
+ * After a call that launched, stllm_last_kernel() names the kernel family and every parameter the dispatcher chose, e.g. "attn_dma_kernel<bf16_t,4,128,512> nw=2
+ * q_lds=1 merge_par=1" (nw: query tiles per workgroup after clipping to the tiles there are), "attn_dma88_kernel<f16_t>", "attn_resident_kernel<bf16_t,96,288>",
+ * "attn_mfma_kernel<bf16_t,96,1>", "attn_mfma_f32_kernel<128,3>", "attn_f32_kernel"; the string lives until the calling thread's next library call.
  */
 int stllm_attention(int dtype, const void* q, int64_t q_bs, int64_t q_rs,
                     const void* k, int64_t k_bs, int64_t k_rs,

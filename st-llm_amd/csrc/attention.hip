@@ -540,6 +540,24 @@ __global__ __launch_bounds__(768) void attn_resident_kernel(const AttnParams p) 
   }
 }
 
+// stllm_last_kernel() after stllm_attention: the kernel family and every parameter its dispatcher chose (the offset / ragged / segment entries name their own)
+template <typename T> constexpr const char* attn_tname();
+template <> constexpr const char* attn_tname<bf16_t>() { return "bf16_t"; }
+template <> constexpr const char* attn_tname<f16_t>() { return "f16_t"; }
+// One per launcher instantiation and thread (static thread_local): the name is formatted when the run-time parameters (key) change, a launch
+// otherwise pays one compare; the string stays valid until the thread's next launch through the same instantiation.
+struct AttnName {
+  char s[96];
+  int key = -1;
+  template <typename... A> const char* get(int k, const char* fmt, A... a) {
+    if (k != key) {
+      snprintf(s, sizeof(s), fmt, a...);
+      key = k;
+    }
+    return s;
+  }
+};
+
 template <typename T, int DP, int SKV_MAX, int KS2 = 1>
 int launch_resident(const AttnParams& p, hipStream_t stream, int nw_req = 0) {
   constexpr int lds = SKV_MAX * (DP * 2 + 16) + DP * (SKV_MAX * 2 + 8);
@@ -561,6 +579,9 @@ int launch_resident(const AttnParams& p, hipStream_t stream, int nw_req = 0) {
     return STLLM_ERR_UNSUPPORTED;
   }
   dim3 grid((q_tiles + nw - 1) / nw, p.H, p.B), block(64 * nw * KS2);
+  static thread_local AttnName name;
+  if (KS2 > 1) stllm_set_last_kernel(name.get(nw, "attn_resident_kernel<%s,%d,%d,%d> nw=%d", attn_tname<T>(), DP, SKV_MAX, KS2, nw));
+  else stllm_set_last_kernel(name.get(0, "attn_resident_kernel<%s,%d,%d>", attn_tname<T>(), DP, SKV_MAX));
   hipLaunchKernelGGL((attn_resident_kernel<T, DP, SKV_MAX, KS2>), grid, block, lds, stream, p);
   STLLM_CHECK_LAUNCH("stllm_attention(resident)");
   return STLLM_OK;
@@ -1048,6 +1069,8 @@ int launch_dma88(const AttnParams& p, hipStream_t stream) {
   const int q_tiles = (p.Sq + 31) / 32;
   const int nw = q_tiles < 12 ? q_tiles : 12;
   dim3 grid((q_tiles + nw - 1) / nw, p.H, p.B), block(64 * nw);
+  static thread_local AttnName name;
+  stllm_set_last_kernel(name.get(0, "attn_dma88_kernel<%s>", attn_tname<T>()));
   hipLaunchKernelGGL((attn_dma88_kernel<T>), grid, block, lds, stream, p);
   STLLM_CHECK_LAUNCH("stllm_attention(dma88)");
   return STLLM_OK;
@@ -1080,6 +1103,9 @@ int launch_dma_nt(const AttnParams& p, hipStream_t stream, int nw_req) {
   const int lds = lds_win + (pp.q_lds ? q_img : 0);
   pp.merge_par = (KS2 > 1 && stllm_options().attn_q_lds != 0 && (KS2 - 1) * nw * (DP / 32 * 16 + 2) * 256 <= lds) ? 1 : 0;
   dim3 grid((q_tiles + nw - 1) / nw, p.H, p.B), block(64 * nw * KS2);
+  static thread_local AttnName name;
+  stllm_set_last_kernel(name.get(nw | pp.q_lds << 8 | pp.merge_par << 9, "attn_dma_kernel<%s,%d,%d,%d> nw=%d q_lds=%d merge_par=%d", attn_tname<T>(), KS2, DP, NT, nw, pp.q_lds,
+                                 pp.merge_par));
   hipLaunchKernelGGL((attn_dma_kernel<T, KS2, DP, NT>), grid, block, lds, stream, pp);
   STLLM_CHECK_LAUNCH("stllm_attention(dma)");
   return STLLM_OK;
@@ -1314,34 +1340,40 @@ __global__ __launch_bounds__(64 * NW) void attn_mfma_f32_kernel(const AttnParams
 }
 
 template <int DP, int NW>
-int launch_mfma_f32(const AttnParams& p, hipStream_t stream) {
+int launch_mfma_f32(const AttnParams& p, hipStream_t stream, bool named = false) {
   dim3 grid((p.Sq + 32 * NW - 1) / (32 * NW), p.H, p.B), block(64 * NW);
+  static thread_local AttnName name;
+  if (named) stllm_set_last_kernel(name.get(0, "attn_mfma_f32_kernel<%d,%d>", DP, NW));
   hipLaunchKernelGGL((attn_mfma_f32_kernel<DP, NW>), grid, block, 0, stream, p);
   STLLM_CHECK_LAUNCH("stllm_attention(fp32 mfma)");
   return STLLM_OK;
 }
 
-// fp32: matrix-core kernel from 8 query rows on (prefill shapes), the vector kernel for the one-row decode step and tiny problems
-int dispatch_f32(const AttnParams& p, hipStream_t stream, int mode) {
+// fp32: matrix-core kernel from 8 query rows on (prefill shapes), the vector kernel for the one-row decode step and tiny problems.
+// named: stllm_attention's call — the launch names itself (stllm_attention_offset has set its own, shorter name before it comes here)
+int dispatch_f32(const AttnParams& p, hipStream_t stream, int mode, bool named = false) {
   if (mode != 0 && p.Sq >= 8) {
     const int nw = p.Sq <= 32 ? 1 : (p.Sq <= 64 ? 2 : 3);
-    if (p.D == 64) return nw == 1 ? launch_mfma_f32<64, 1>(p, stream) : nw == 2 ? launch_mfma_f32<64, 2>(p, stream) : launch_mfma_f32<64, 3>(p, stream);
-    if (p.D == 88) return nw == 1 ? launch_mfma_f32<96, 1>(p, stream) : nw == 2 ? launch_mfma_f32<96, 2>(p, stream) : launch_mfma_f32<96, 3>(p, stream);
-    if (p.D == 128) return nw == 1 ? launch_mfma_f32<128, 1>(p, stream) : nw == 2 ? launch_mfma_f32<128, 2>(p, stream) : launch_mfma_f32<128, 3>(p, stream);
+    if (p.D == 64) return nw == 1 ? launch_mfma_f32<64, 1>(p, stream, named) : nw == 2 ? launch_mfma_f32<64, 2>(p, stream, named) : launch_mfma_f32<64, 3>(p, stream, named);
+    if (p.D == 88) return nw == 1 ? launch_mfma_f32<96, 1>(p, stream, named) : nw == 2 ? launch_mfma_f32<96, 2>(p, stream, named) : launch_mfma_f32<96, 3>(p, stream, named);
+    if (p.D == 128) return nw == 1 ? launch_mfma_f32<128, 1>(p, stream, named) : nw == 2 ? launch_mfma_f32<128, 2>(p, stream, named) : launch_mfma_f32<128, 3>(p, stream, named);
   }
   if (p.Skv > kF32MaxKv) {
     stllm_set_error("stllm_attention(fp32, vector kernel): Skv %d > %d", p.Skv, kF32MaxKv);
     return STLLM_ERR_BAD_SHAPE;
   }
   dim3 grid((p.Sq + 3) / 4, p.H, p.B), block(256);
+  if (named) stllm_set_last_kernel("attn_f32_kernel");
   hipLaunchKernelGGL(attn_f32_kernel, grid, block, 0, stream, p);
   STLLM_CHECK_LAUNCH("stllm_attention(fp32)");
   return STLLM_OK;
 }
 
 template <typename T, int DP, int NW>
-int launch_mfma(const AttnParams& p, hipStream_t stream) {
+int launch_mfma(const AttnParams& p, hipStream_t stream, bool named = false) {   // named: as in dispatch_f32
   dim3 grid((p.Sq + 32 * NW - 1) / (32 * NW), p.H, p.B), block(64 * NW);
+  static thread_local AttnName name;
+  if (named) stllm_set_last_kernel(name.get(0, "attn_mfma_kernel<%s,%d,%d>", attn_tname<T>(), DP, NW));
   hipLaunchKernelGGL((attn_mfma_kernel<T, DP, NW>), grid, block, 0, stream, p);
   STLLM_CHECK_LAUNCH("stllm_attention");
   return STLLM_OK;
@@ -1352,7 +1384,7 @@ int dispatch(const AttnParams& p, hipStream_t stream) {
   // NW picked so that 32*NW divides the common sequence lengths with little waste:
   //   ViT 257 -> 3 waves (96 rows, 3 blocks), Q-Former 32/44 -> 1-2 waves, Llama -> 3 waves (576 = 6*96)
   if (p.D == 88) {
-    if (p.Sq <= 32) return launch_mfma<T, 96, 1>(p, stream);                       // BT-Adapter temporal attention
+    if (p.Sq <= 32) return launch_mfma<T, 96, 1>(p, stream, true);                 // BT-Adapter temporal attention
     if (p.Skv <= 288 && !p.causal) {
       const int g_attn_dma = stllm_options().attn_dma;
       const bool al = ((reinterpret_cast<uintptr_t>(p.k) | reinterpret_cast<uintptr_t>(p.v)) & 15) == 0 && (p.k_rs % 8) == 0 && (p.v_rs % 8) == 0 &&
@@ -1362,9 +1394,9 @@ int dispatch(const AttnParams& p, hipStream_t stream) {
       if (g_attn_dma != 0 && al) return launch_dma88<T>(p, stream);
       return launch_resident<T, 96, 288>(p, stream);
     }  // ViT: K/V of a head resident in LDS (a key split here re-stages K/V per query chunk: 26 -> 37 us)
-    return launch_mfma<T, 96, 3>(p, stream);
+    return launch_mfma<T, 96, 3>(p, stream, true);
   }
-  if (p.D == 64) return p.Sq <= 32 ? launch_mfma<T, 64, 1>(p, stream) : launch_mfma<T, 64, 2>(p, stream);
+  if (p.D == 64) return p.Sq <= 32 ? launch_mfma<T, 64, 1>(p, stream, true) : launch_mfma<T, 64, 2>(p, stream, true);
   if (p.D == 128) {
     const int g_attn_dma = stllm_options().attn_dma;
     const bool al = ((reinterpret_cast<uintptr_t>(p.k) | reinterpret_cast<uintptr_t>(p.v)) & 15) == 0 && (p.k_rs % 8) == 0 && (p.v_rs % 8) == 0 &&
@@ -1703,7 +1735,7 @@ extern "C" int stllm_attention(int dtype, const void* q, int64_t q_bs, int64_t q
   switch (dtype) {
     case STLLM_BF16: return dispatch<bf16_t>(p, stream);
     case STLLM_F16: return dispatch<f16_t>(p, stream);
-    case STLLM_F32: return dispatch_f32(p, stream, stllm_options().attn_f32_mfma);
+    case STLLM_F32: return dispatch_f32(p, stream, stllm_options().attn_f32_mfma, true);
   }
   stllm_set_error("stllm_attention: bad dtype %d", dtype);
   return STLLM_ERR_BAD_DTYPE;
