@@ -738,6 +738,52 @@ typedef struct stllm_beam_args {
 } stllm_beam_args;
 int stllm_beam_candidates(const stllm_beam_args* args, void* stream);
 
+/*
+ * Token selection with per-slot state (serving.Engine(state="device")): stllm_select_tokens for the slots of a continuous batch, each
+ * with its own step count, history, EOS suppression, token budget and stop-sequence match.  ONE launch, one workgroup per slot; staging, reductions, LDS
+ * limit and error behaviour are stllm_select_tokens' (the row body is the same device function).  (V + ld_ids) * 4 bytes must fit the LDS limit above —
+ * a whole history, whatever the slots hold in this step: otherwise STLLM_ERR_UNSUPPORTED.
+ *
+ * src[s] is the row of `logits` that belongs to slot s in this step; src[s] < 0 or >= rows: the slot is NOT SERVED — nothing of it is read (not its
+ * state, ids, u) and nothing is written.  state[s] = (live, n_gen, max_new, pending), in / out.
+ *   A served slot with live == 0: pending = pad_id; nothing else is read or written (its ids, u and aux are untouched).
+ *   A served slot with live != 0, c = n_gen clamped to [0, ld_ids - 1]:
+ *     token = steps 1 - 3 of stllm_select_tokens on logits[src[s], :V] with prev = ids[s, :c], n_prev = c, suppress_eos = (eos_id >= 0 && n_gen < min_length)
+ *             and u[s];
+ *     ids[s, c] = token, n_gen = c + 1, pending = token;
+ *     live = 0 iff token == eos_id, or c + 1 >= max_new, or ids[s, :c + 1] ends in stops[j, :stop_len[j]] for some j with 0 < stop_len[j] <= c + 1
+ *             (and stop_len[j] <= ld_stop); otherwise live = 1.
+ *     aux[s] (nullable, float [n_slots, 4]) as stllm_select_tokens writes it.
+ * Token and aux of a live served slot are bit-identical to a stllm_select_tokens launch of that row alone with that slot's n_prev, suppress_eos and u.
+ * Never read: logits columns >= V and rows that no src names; ids[s, j] for j >= n_gen (they may hold anything); stops[j, i] for i >= stop_len[j];
+ * u unless sample.  Never written: logits, src, u, stops, stop_len; ids other than ids[s, c]; anything of a slot that is not served.  Two slots may
+ * name the same row: rows are only read.
+ */
+typedef struct stllm_select_slots_args {
+  const float* logits;       /* [rows, ldl] fp32 */
+  int64_t ldl;               /* row stride in floats (>= V; any alignment) */
+  int rows, V;
+  int n_slots;
+  const int32_t* src;        /* [n_slots] logits row of the slot in this step; outside [0, rows): not served */
+  int32_t* state;            /* [n_slots, 4] (live, n_gen, max_new, pending), in / out */
+  int32_t* ids;              /* [n_slots, ld_ids] generated history, in / out */
+  int64_t ld_ids;            /* >= 1 */
+  float penalty;             /* 1: none */
+  int min_length;
+  int eos_id;                /* < 0: none */
+  int pad_id;
+  int sample;                /* 0 greedy, 1 top-p sampling */
+  float temperature;         /* > 0 */
+  float top_p;
+  const float* u;            /* [n_slots], sample only */
+  const int32_t* stops;      /* [n_stop, ld_stop]; may be NULL when n_stop == 0 */
+  int64_t ld_stop;
+  const int32_t* stop_len;   /* [n_stop] */
+  int n_stop;
+  float* aux;                /* nullable, [n_slots, 4] */
+} stllm_select_slots_args;
+int stllm_select_slots(const stllm_select_slots_args* args, void* stream);
+
 /* =========================================================================================================================
  * Backward / optimizer entry points.  The reference has no such code of its own: the gradients come
  * from torch.autograd over st_llm.py:116-146 (shifted CE + loss_mvm) driven by HF Trainer + DeepSpeed (train_hf.py,

@@ -208,24 +208,77 @@ __device__ __forceinline__ void sel_penalise(float* s, float* pv, const int32_t*
   __syncthreads();
 }
 
-__global__ __launch_bounds__(kSelThreads) void select_tokens_kernel(const stllm_select_args a) {
+// One kernel body for stllm_select_tokens (SLOTS = false: workgroup = row r of every table, one step index for the launch) and stllm_select_slots
+// (SLOTS = true: workgroup = slot, which reads logits row src[slot] behind its own history, step count and EOS suppression, and whose thread 0 appends
+// the token and updates the slot's state row at the end).  Everything between the staging and the token is the same code: steps 1 - 3 of the header.
+template <bool SLOTS> struct SelArgs { typedef stllm_select_args type; };
+template <> struct SelArgs<true> { typedef stllm_select_slots_args type; };
+
+// stllm_select_slots, thread 0: the token is appended at ids[c]; `live` drops on EOS, at the budget, or when the history now ends in a stop sequence (its
+// last id is this step's token, the others are ids[c + 1 - n ..])
+__device__ __forceinline__ void sel_slot_update(const stllm_select_slots_args& a, int32_t* st, int32_t* hist, int c, int max_new, int tok) {
+  int live = (tok == a.eos_id || c + 1 >= max_new) ? 0 : 1;
+  for (int j = 0; live && j < a.n_stop; ++j) {
+    const int n = a.stop_len[j];
+    if (n <= 0 || n > c + 1 || n > a.ld_stop) continue;
+    const int32_t* sq = a.stops + (int64_t)j * a.ld_stop;
+    bool hit = sq[n - 1] == tok;
+    for (int i = 0; hit && i < n - 1; ++i) hit = hist[c + 1 - n + i] == sq[i];
+    if (hit) live = 0;
+  }
+  hist[c] = tok;
+  st[1] = c + 1;
+  st[3] = tok;
+  st[0] = live;
+}
+
+template <bool SLOTS>
+__global__ __launch_bounds__(kSelThreads) void select_kernel(const typename SelArgs<SLOTS>::type a) {
   extern __shared__ float smem[];                 // [V] scores, then [n_prev] penalised values
   __shared__ SelRed red;
   __shared__ float csum[kSelThreads];             // per-chunk kept sums, then their inclusive prefix
   __shared__ int clast[kSelThreads];              // last kept id of a chunk, -1: none
   __shared__ float gbase[kSelThreads / 16];
-  const int row = blockIdx.x, tid = threadIdx.x, V = a.V;
-  int32_t* out = a.out + (int64_t)row * a.out_stride;
-  if (a.unfinished && a.unfinished[row] == 0) {   // a finished row emits pad (uniform over the block)
-    if (tid == 0) *out = a.pad_id;
-    return;
+  int row = blockIdx.x;                           // of u and aux (the slot), and of every other table of stllm_select_tokens
+  const int tid = threadIdx.x, V = a.V;
+  // what differs between the two entry points, set once: where the token goes, the logits row, the history and the EOS suppression
+  int32_t* out = nullptr;
+  int32_t *st = nullptr, *hist = nullptr;
+  int hist_n = 0, max_new = 0;
+  const float* x;
+  const int32_t* prev;
+  int n_prev;
+  bool suppress_eos;
+  if constexpr (SLOTS) {
+    const int r = a.src[row];
+    if (r < 0 || r >= a.rows) return;             // not served in this step (uniform over the block): nothing else is read
+    st = a.state + (int64_t)row * 4;              // (live, n_gen, max_new, pending): read here by every thread, written by thread 0 behind the barriers
+    if (st[0] == 0) {
+      if (tid == 0) st[3] = a.pad_id;
+      return;
+    }
+    const int n_gen = st[1];
+    max_new = st[2];
+    hist_n = min(max(n_gen, 0), (int)a.ld_ids - 1);
+    hist = a.ids + (int64_t)row * a.ld_ids;
+    x = a.logits + (int64_t)r * a.ldl;
+    prev = hist; n_prev = hist_n;
+    suppress_eos = a.eos_id >= 0 && n_gen < a.min_length;
+  } else {
+    out = a.out + (int64_t)row * a.out_stride;
+    if (a.unfinished && a.unfinished[row] == 0) {   // a finished row emits pad (uniform over the block)
+      if (tid == 0) *out = a.pad_id;
+      return;
+    }
+    x = a.logits + (int64_t)row * a.ldl;
+    prev = a.prev + (int64_t)row * a.ld_prev; n_prev = a.n_prev;
+    suppress_eos = a.suppress_eos;
   }
   float* s = smem;
-  const float* x = a.logits + (int64_t)row * a.ldl;
   for (int c = tid; c < V; c += kSelThreads) s[c] = x[c];
   __syncthreads();
-  if (a.penalty != 1.0f && a.n_prev > 0) sel_penalise(s, s + V, a.prev + (int64_t)row * a.ld_prev, a.n_prev, V, a.penalty);
-  if (a.suppress_eos && tid == 0 && (unsigned)a.eos_id < (unsigned)V) s[a.eos_id] = -INFINITY;
+  if (a.penalty != 1.0f && n_prev > 0) sel_penalise(s, s + V, prev, n_prev, V, a.penalty);
+  if (suppress_eos && tid == 0 && (unsigned)a.eos_id < (unsigned)V) s[a.eos_id] = -INFINITY;
   __syncthreads();
   // from here to the chunked walk a thread touches only the columns c = tid (mod 256): no barrier is needed between those passes
   const bool sample = a.sample != 0;
@@ -248,8 +301,12 @@ __global__ __launch_bounds__(kSelThreads) void select_tokens_kernel(const stllm_
       if (tid == 0) { float* ax = a.aux + (int64_t)row * 4; ax[0] = mx; ax[1] = logf(z); ax[2] = 0.0f; ax[3] = 1.0f; }
     }
     if (tid == 0) {
-      *out = amax;
-      if (a.unfinished && amax == a.eos_id) a.unfinished[row] = 0;
+      if constexpr (SLOTS) {
+        sel_slot_update(a, st, hist, hist_n, max_new, amax);
+      } else {
+        *out = amax;
+        if (a.unfinished && amax == a.eos_id) a.unfinished[row] = 0;
+      }
     }
     return;
   }
@@ -320,8 +377,12 @@ __global__ __launch_bounds__(kSelThreads) void select_tokens_kernel(const stllm_
     }
     break;
   }
-  *out = tok;
-  if (a.unfinished && tok == a.eos_id) a.unfinished[row] = 0;
+  if constexpr (SLOTS) {
+    sel_slot_update(a, st, hist, hist_n, max_new, tok);
+  } else {
+    *out = tok;
+    if (a.unfinished && tok == a.eos_id) a.unfinished[row] = 0;
+  }
   if (a.aux) {
     float* ax = a.aux + (int64_t)row * 4;
     ax[0] = mx; ax[1] = logf(Z); ax[2] = __builtin_bit_cast(float, tb); ax[3] = __fdiv_rn(Zk, Z);
@@ -396,14 +457,14 @@ extern "C" int stllm_select_tokens(const stllm_select_args* a, void* stream) {
   bool lds_first;
   const int lds_d = lds_dev.enter(&lds_first);
   if (lds_first || lds > lds_dev.value[lds_d]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(select_tokens_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(select_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
       stllm_set_error("stllm_select_tokens: cannot opt into %d bytes of LDS", lds);
       return STLLM_ERR_UNSUPPORTED;
     }
     lds_dev.value[lds_d] = lds;
     lds_dev.done(lds_d);
   }
-  hipLaunchKernelGGL(select_tokens_kernel, dim3(a->rows), dim3(kSelThreads), lds, reinterpret_cast<hipStream_t>(stream), *a);
+  hipLaunchKernelGGL(select_kernel<false>, dim3(a->rows), dim3(kSelThreads), lds, reinterpret_cast<hipStream_t>(stream), *a);
   STLLM_CHECK_LAUNCH("stllm_select_tokens");
   return STLLM_OK;
 }
@@ -433,6 +494,37 @@ extern "C" int stllm_beam_candidates(const stllm_beam_args* a, void* stream) {
   }
   hipLaunchKernelGGL(beam_candidates_kernel, dim3(a->rows), dim3(kSelThreads), lds, reinterpret_cast<hipStream_t>(stream), *a);
   STLLM_CHECK_LAUNCH("stllm_beam_candidates");
+  return STLLM_OK;
+}
+
+extern "C" int stllm_select_slots(const stllm_select_slots_args* a, void* stream) {
+  STLLM_CHECK_ARG(a != nullptr, "stllm_select_slots: null args");
+  STLLM_CHECK_ARG(a->logits && a->rows > 0 && a->V > 0 && a->ldl >= a->V, "stllm_select_slots: bad logits / rows=%d V=%d ldl=%lld", a->rows, a->V,
+                  (long long)a->ldl);
+  STLLM_CHECK_ARG(a->n_slots > 0 && a->src && a->state && a->ids && a->ld_ids >= 1, "stllm_select_slots: bad src / state / ids / n_slots=%d ld_ids=%lld",
+                  a->n_slots, (long long)a->ld_ids);
+  STLLM_CHECK_ARG(a->n_stop >= 0 && (a->n_stop == 0 || (a->stops && a->stop_len && a->ld_stop >= 1)), "stllm_select_slots: stops needs stop_len and ld_stop >= 1");
+  STLLM_CHECK_ARG(a->penalty > 0.0f, "stllm_select_slots: penalty must be positive");
+  STLLM_CHECK_ARG(!a->sample || (a->u && a->temperature > 0.0f && a->top_p > 0.0f), "stllm_select_slots(sample): needs u, temperature > 0, top_p > 0");
+  const int64_t need = ((int64_t)a->V + a->ld_ids) * 4;   // the row and a whole history, whatever the slots hold in this step
+  if (need > kSelLdsBytes) {
+    stllm_set_error("stllm_select_slots: V=%d + ld_ids=%lld floats do not fit %d bytes of LDS", a->V, (long long)a->ld_ids, kSelLdsBytes);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  const int lds = (int)((need + 15) & ~(int64_t)15);
+  static StllmPerDevice lds_dev;   // largest dynamic-LDS size opted into, per device ordinal
+  bool lds_first;
+  const int lds_d = lds_dev.enter(&lds_first);
+  if (lds_first || lds > lds_dev.value[lds_d]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(select_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+      stllm_set_error("stllm_select_slots: cannot opt into %d bytes of LDS", lds);
+      return STLLM_ERR_UNSUPPORTED;
+    }
+    lds_dev.value[lds_d] = lds;
+    lds_dev.done(lds_d);
+  }
+  hipLaunchKernelGGL(select_kernel<true>, dim3(a->n_slots), dim3(kSelThreads), lds, reinterpret_cast<hipStream_t>(stream), *a);
+  STLLM_CHECK_LAUNCH("stllm_select_slots");
   return STLLM_OK;
 }
 

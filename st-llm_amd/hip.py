@@ -31,7 +31,7 @@ EXPORTS = ["stllm_last_error", "stllm_abi_version", "stllm_last_kernel", "stllm_
            "stllm_attention_decode_ragged_workspace_bytes", "stllm_attention_decode_ragged", "stllm_kv_append_rows",
            "stllm_attention_shared_workspace_bytes", "stllm_attention_shared", "stllm_select_tokens", "stllm_beam_candidates",
            "stllm_attention_offset_ragged_workspace_bytes", "stllm_attention_offset_ragged", "stllm_kv_append_spans",
-           "stllm_attention_segments_workspace_bytes", "stllm_attention_segments", "stllm_kv_append_segments"]
+           "stllm_attention_segments_workspace_bytes", "stllm_attention_segments", "stllm_kv_append_segments", "stllm_select_slots"]
 
 
 def torch_dtype(d):
@@ -79,6 +79,14 @@ class SelectArgs(ctypes.Structure):
     _fields_ = [("logits", c_void_p), ("ldl", c_int64), ("rows", c_int), ("V", c_int), ("prev", c_void_p), ("ld_prev", c_int64), ("n_prev", c_int),
                 ("penalty", c_float), ("suppress_eos", c_int), ("eos_id", c_int), ("pad_id", c_int), ("sample", c_int), ("temperature", c_float),
                 ("top_p", c_float), ("u", c_void_p), ("unfinished", c_void_p), ("out", c_void_p), ("out_stride", c_int64), ("aux", c_void_p)]
+
+
+class SelectSlotsArgs(ctypes.Structure):
+    """stllm_select_slots_args (include/stllm_hip.h)"""
+    _fields_ = [("logits", c_void_p), ("ldl", c_int64), ("rows", c_int), ("V", c_int), ("n_slots", c_int), ("src", c_void_p), ("state", c_void_p),
+                ("ids", c_void_p), ("ld_ids", c_int64), ("penalty", c_float), ("min_length", c_int), ("eos_id", c_int), ("pad_id", c_int), ("sample", c_int),
+                ("temperature", c_float), ("top_p", c_float), ("u", c_void_p), ("stops", c_void_p), ("ld_stop", c_int64), ("stop_len", c_void_p),
+                ("n_stop", c_int), ("aux", c_void_p)]
 
 
 class BeamArgs(ctypes.Structure):
@@ -218,6 +226,7 @@ def _bind(L, strict=True):
     B("stllm_gemv_q4", [ctypes.POINTER(GemvQ4Args), c_void_p])
     B("stllm_select_tokens", [ctypes.POINTER(SelectArgs), c_void_p])
     B("stllm_beam_candidates", [ctypes.POINTER(BeamArgs), c_void_p])
+    B("stllm_select_slots", [ctypes.POINTER(SelectSlotsArgs), c_void_p])
     B("stllm_gemm_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     B("stllm_gemm_w4_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     return L
@@ -1241,6 +1250,46 @@ def select_tokens(logits, out, *, prev=None, n_prev=0, penalty=1.0, suppress_eos
                    aux=aux.data_ptr() if aux is not None else None)
     _check(lib().stllm_select_tokens(ctypes.byref(a), _stream()), "stllm_select_tokens")
     return out
+
+
+def select_slots(logits, src, state, ids, *, penalty=1.0, min_length=0, eos_id=None, pad_id=0, sample=False, temperature=1.0, top_p=1.0, u=None, stops=None,
+                 stop_len=None, aux=None):
+    """stllm_select_slots: one launch selects the next token of every SERVED slot of a continuous batch.  logits f32 [rows, V]; src int32 [n_slots]: slot s
+    reads row src[s] (outside [0, rows): not served, untouched); state int32 [n_slots, 4] = (live, n_gen, max_new, pending) and ids int32 [n_slots, ld_ids],
+    both in / out: a live slot appends its token at ids[s, n_gen], counts it, leaves it in `pending` and drops `live` on EOS, at max_new or when its ids end
+    in a row of stops int32 [n_stop, ld_stop] (stop_len int32 [n_stop]); a dead served slot gets pending = pad_id.  EOS is suppressed while n_gen <
+    min_length; u f32 [n_slots] drives sampling; aux f32 [n_slots, 4] (optional) as select_tokens.  V + ld_ids floats that do not fit the LDS raise."""
+    _req(logits, torch.float32, "logits")
+    if logits.dim() != 2:
+        raise RuntimeError(f"select_slots: logits must be [rows, V], got {tuple(logits.shape)}")
+    rows, V = logits.shape
+    ldl = logits.stride(0) if rows > 1 else max(logits.stride(0), V)
+    _req(src, torch.int32, "src"); _req(state, torch.int32, "state"); _req(ids, torch.int32, "ids")
+    n_slots = src.numel()
+    if src.dim() != 1 or not src.is_contiguous() or tuple(state.shape) != (n_slots, 4) or not state.is_contiguous():
+        raise RuntimeError(f"select_slots: src must be contiguous int32 [n_slots], state contiguous int32 [n_slots, 4]; got {tuple(src.shape)}, {tuple(state.shape)}")
+    if ids.dim() != 2 or ids.shape[0] != n_slots or ids.shape[1] < 1 or not ids.is_contiguous():
+        raise RuntimeError(f"select_slots: ids must be contiguous int32 [{n_slots}, ld_ids >= 1], got {tuple(ids.shape)}")
+    if sample:
+        _req(u, torch.float32, "u")
+        if u.numel() != n_slots or not u.is_contiguous():
+            raise RuntimeError("select_slots(sample): u must be contiguous f32 [n_slots]")
+    n_stop = 0 if stops is None else stops.shape[0]
+    if n_stop:
+        _req(stops, torch.int32, "stops"); _req(stop_len, torch.int32, "stop_len")
+        if stops.dim() != 2 or stops.shape[1] < 1 or not stops.is_contiguous() or stop_len.numel() != n_stop or not stop_len.is_contiguous():
+            raise RuntimeError("select_slots: stops must be contiguous int32 [n_stop, ld_stop >= 1], stop_len contiguous int32 [n_stop]")
+    if aux is not None:
+        _req(aux, torch.float32, "aux")
+        if tuple(aux.shape) != (n_slots, 4) or not aux.is_contiguous():
+            raise RuntimeError("select_slots: aux must be contiguous f32 [n_slots, 4]")
+    a = SelectSlotsArgs(logits=logits.data_ptr(), ldl=ldl, rows=rows, V=V, n_slots=n_slots, src=src.data_ptr(), state=state.data_ptr(), ids=ids.data_ptr(),
+                        ld_ids=ids.shape[1], penalty=penalty, min_length=int(min_length),
+                        eos_id=-1 if eos_id is None else int(eos_id), pad_id=int(pad_id), sample=int(bool(sample)), temperature=temperature, top_p=top_p,
+                        u=u.data_ptr() if sample else None, stops=stops.data_ptr() if n_stop else None, ld_stop=stops.shape[1] if n_stop else 0,
+                        stop_len=stop_len.data_ptr() if n_stop else None, n_stop=n_stop, aux=aux.data_ptr() if aux is not None else None)
+    _check(lib().stllm_select_slots(ctypes.byref(a), _stream()), "stllm_select_slots")
+    return state
 
 
 def beam_candidates(logits, beam_score, k, *, prev=None, n_prev=0, penalty=1.0, suppress_eos=False, eos_id=None, cand_score=None, cand_token=None):

@@ -12,8 +12,14 @@ batch.  The Engine owns one KVCache of `slots` rows instead.  Every step it free
 Selection is per request, with generate()'s own processors (generation._process_logits / _warp_logits) on that request's ids and step count: a request
 generates the ids that generate() gives for it alone (greedy; sampling with its own generator).
 
-Not served (they raise): beams, selection="device" (stllm_select_tokens takes one step index for all rows), share_prefix / caches with a base,
-return_cache.  No paged blocks, no preemption: a request must fit `max_len` positions when it is submitted and keeps its slot until it finishes."""
+Engine(state="device") keeps that per-request state on the device instead: a [slots, 4] table (live, n_gen, max_new, pending), the
+generated ids [slots, max_new] and the stop sequences.  ONE hip.select_slots launch behind the pass selects for every served slot with its own step count,
+appends the token and settles whether the request is finished; the next step's embeddings are gathered from the table's `pending` column.  The host reads
+the table once per step, and a request's ids once, when it finishes.  A request generates the ids of generate(selection="device") for it alone.
+
+Not served (they raise): beams, selection="device" among the options (the device path of the Engine is state="device"), share_prefix / caches with a base,
+return_cache; with state="device" also stopping_criteria (Python callables need the ids on the host) and sync_every != 1.  No paged blocks, no preemption:
+a request must fit `max_len` positions when it is submitted and keeps its slot until it finishes."""
 import collections
 
 import torch
@@ -32,14 +38,19 @@ class _Request:
 
 class Engine:
     """Engine(lm_wrapper, slots, max_len, **options): `lm_wrapper` is what generate() runs on (`.model` a LlamaModel, `.logits_from`), `options` are
-    generate()'s sampling and stopping options (generation.Options); num_beams == 1, use_cache and selection == "torch" only."""
+    generate()'s sampling and stopping options (generation.Options); num_beams == 1, use_cache and selection == "torch" only.
+    state: "host" (default) selects per request on the host with generate()'s processors; "device" keeps the per-request selection state on the device
+    and selects for all slots in one hip.select_slots launch (see the module docstring)."""
 
-    def __init__(self, lm_wrapper, slots, max_len, device=None, **options):
+    def __init__(self, lm_wrapper, slots, max_len, device=None, state="host", **options):
         o = generation.Options(**options)
+        if state not in ("host", "device"):
+            raise ValueError(f"serving.Engine: state must be 'host' or 'device', got {state!r}")
         if o.num_beams != 1:
             raise NotImplementedError("serving.Engine: beams are not served (num_beams == 1)")
         if o.selection != "torch":
-            raise NotImplementedError("serving.Engine: selection='device' is not served (stllm_select_tokens takes one step index for all rows)")
+            raise NotImplementedError("serving.Engine: selection='device' is generate()'s fixed-batch path (stllm_select_tokens takes one step index for all "
+                                      "rows); the Engine selects on the device with Engine(..., state='device')")
         if not o.use_cache:
             raise ValueError("serving.Engine: needs use_cache (the slots ARE the KV cache)")
         if o.share_prefix or o.return_cache or o.return_lengths:
@@ -56,6 +67,9 @@ class Engine:
         self.free = list(range(slots))
         self.handles = 0
         self.steps = collections.Counter()   # "segments" / "decode": the passes run so far
+        self.state = state
+        if state == "device":
+            self._init_device_state(slots)
 
     # ---- requests ------------------------------------------------------------------------------------------------------------------------------
     def submit(self, inputs_embeds, prefix=None, max_new_tokens=None, generator=None):
@@ -72,6 +86,10 @@ class Engine:
         need = P + inputs_embeds.shape[0] + max_new - 1      # the last generated token is never fed
         if need > self.cache.max_len:
             raise ValueError(f"serving.Engine.submit: the request needs {need} positions (prefix + prompt + max_new_tokens - 1), a slot holds {self.cache.max_len}")
+        if self.state == "device" and max_new > self.d_ids.shape[1]:   # a longer budget than any so far: widen the id table (a device copy, no read)
+            ids = torch.zeros((self.d_ids.shape[0], max_new), dtype=torch.int32, device=self.device)
+            ids[:, :self.d_ids.shape[1]] = self.d_ids
+            self.d_ids = ids
         self.handles += 1
         self.queue.append(_Request(self.handles, inputs_embeds.float().to(self.device), prefix, max_new, generator if generator is not None else self.o.generator))
         return self.handles
@@ -84,6 +102,8 @@ class Engine:
     def step(self):
         """release, admit, one decoder pass, one selected token per request in a slot.  Returns [(handle, ids)] of the requests that finished in this
         step: ids is the 1-D LongTensor generate() returns for that request alone."""
+        if self.state == "device":
+            return self._step_device()
         for s in self.done_slots:
             self.cache.release(s)
             self.free.append(s)
@@ -155,8 +175,112 @@ class Engine:
         out = []
         while not self.idle():
             out += self.step()
+        self._release_done()
+        return out
+
+    # ---- state="device" ------------------------------------------------------------------------------------------------------------------------
+    def _init_device_state(self, slots):
+        from . import hip
+        o = self.o
+        if o.stopping_criteria is not None:
+            raise NotImplementedError("serving.Engine(state='device'): stopping_criteria are Python callables on host ids; use stop_sequences, or state='host'")
+        if int(o.sync_every) != 1:
+            raise NotImplementedError("serving.Engine(state='device'): sync_every != 1 is not served (the state table is read every step)")
+        dev = self.device
+        self.d_state = torch.zeros((slots, 4), dtype=torch.int32, device=dev)     # (live, n_gen, max_new, pending) per slot
+        self.d_state[:, 3] = o.pad_token_id
+        self.d_ids = torch.zeros((slots, max(1, int(o.max_new_tokens))), dtype=torch.int32, device=dev)
+        self.d_pending = torch.empty(slots, dtype=torch.int32, device=dev)        # the gather's index operand: a dense copy of the pending column
+        self.d_u = torch.zeros(slots, dtype=torch.float32, device=dev)
+        self.d_stops = self.d_stop_len = None
+        stops = [s.reshape(-1).tolist() for s in (o.stop_sequences or []) if s.numel()]
+        if stops:
+            table = torch.zeros((len(stops), max(len(s) for s in stops)), dtype=torch.int32)
+            for j, s in enumerate(stops):
+                table[j, :len(s)] = torch.tensor(s, dtype=torch.int32)
+            self.d_stops = table.to(dev)
+            self.d_stop_len = torch.tensor([len(s) for s in stops], dtype=torch.int32).to(dev)
+        self._h2d = lambda rows: hip.h2d(torch.tensor(rows, dtype=torch.int32), dev)   # a small int32 table, uploaded without stalling the host
+
+    def _release_done(self):
         for s in self.done_slots:
             self.cache.release(s)
             self.free.append(s)
+            if self.state == "device":            # the slot's row: dead, and what it feeds while it rides along is pad (an upload, never a read)
+                self.d_state[s].copy_(self._h2d([0, 0, 0, self.o.pad_token_id]))
         self.done_slots = []
-        return out
+
+    def _read_state(self):
+        """the ONE device-to-host transfer of a state="device" step: the [slots, 4] table as lists"""
+        return self.d_state.tolist()
+
+    def _step_device(self):
+        """step() with the selection state on the device: release, admit, one decoder pass fed from the table's `pending` column, ONE hip.select_slots launch,
+        one read of the table"""
+        from . import hip
+        o, K, dev = self.o, self.cache.batch, self.device
+        self._release_done()
+        self.free.sort()
+        admitted = []
+        while self.queue and self.free:
+            r = self.queue.popleft()
+            r.slot = self.free.pop(0)
+            if r.prefix is not None:
+                self.cache.load_row(r.slot, r.prefix)
+            self.d_state[r.slot].copy_(self._h2d([1, 0, r.max_new, o.pad_token_id]))
+            admitted.append(r)
+        if not admitted and not self.running:
+            return []
+        running = [self.running[s] for s in sorted(self.running)]
+        table = self.lm.embed_tokens.weight
+        src = [-1] * K                            # slot -> its row of this step's logits
+        if admitted:
+            parts, segments = [], []
+            if running:
+                pending = torch.index_select(self.d_state[:, 3], 0, self._h2d([r.slot for r in running]))
+                parts.append(hip.gather_rows(table, pending.to(table.device)).to(dev))
+                segments += [(r.slot, 1) for r in running]
+            for r in admitted:
+                parts.append(r.emb)
+                segments.append((r.slot, r.emb.shape[0]))
+                self.running[r.slot] = r
+                r.emb = None
+            _, h16 = self.lm.step_segments(torch.cat(parts) if len(parts) > 1 else parts[0], self.cache, segments)
+            served = running + admitted
+            logits = self.m.logits_from(h16, len(served), 1)[:, 0]
+            for i, r in enumerate(served):
+                src[r.slot] = i
+            self.steps["segments"] += 1
+        else:
+            self.d_pending.copy_(self.d_state[:, 3])
+            _, h16 = self.lm.decode_step(hip.gather_rows(table, self.d_pending.to(table.device)).to(dev).view(K, 1, -1), self.cache)
+            for s in self.free:                   # the free slots rode along: whatever they appended is don't-care
+                self.cache.release(s)
+            logits = self.m.logits_from(h16, K, 1)[:, 0]
+            served = running
+            for r in served:
+                src[r.slot] = r.slot
+            self.steps["decode"] += 1
+        if o.do_sample:                           # one draw per served request from ITS generator: the stream generate(selection="device") consumes for it alone
+            draws = [torch.rand(1, generator=r.generator, device=r.generator.device if r.generator is not None else dev) for r in served]
+            if all(d.device.type == "cpu" for d in draws):
+                u = torch.zeros(K)
+                u[torch.tensor([r.slot for r in served])] = torch.cat(draws)
+                self.d_u.copy_(hip.h2d(u, dev))   # one upload per step
+            else:
+                for r, d in zip(served, draws):
+                    self.d_u[r.slot:r.slot + 1].copy_(d)
+        hip.select_slots(logits, self._h2d(src), self.d_state, self.d_ids, penalty=o.repetition_penalty, min_length=o.min_length, eos_id=o.eos_token_id,
+                         pad_id=o.pad_token_id, sample=o.do_sample, temperature=o.temperature, top_p=o.top_p, u=self.d_u if o.do_sample else None,
+                         stops=self.d_stops, stop_len=self.d_stop_len)
+        state = self._read_state()
+        finished = []
+        for r in served:
+            live, n_gen = state[r.slot][0], state[r.slot][1]
+            if not live:
+                finished.append((r.handle, self.d_ids[r.slot, :n_gen].long()))
+                del self.running[r.slot]
+                self.done_slots.append(r.slot)
+        if finished and dev.type == "cuda":
+            hip.gemm_workspace_check(dev, wait=True)   # as generation._finish: no id leaves behind a timed-out split-K exchange
+        return finished

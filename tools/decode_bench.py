@@ -32,6 +32,8 @@ ap.add_argument("--cases", default="", help="with --generate: several workloads 
 ap.add_argument("--sync-every", type=int, default=1, help="with --generate, selection 'device': generate(sync_every=K)")
 ap.add_argument("--serve", default="", help="N,K: N questions behind one prefilled --prefix-len prefix through K slots of serving.Engine (continuous batching) against "
                                             "generate(batching='ragged') in waves of K; mixed answer lengths (printed), EOS disabled, useful tokens/s of both")
+ap.add_argument("--state", choices=["host", "device", "both"], default="host", help="with --serve: serving.Engine(state=...); 'both' alternates the host-state and the "
+                "device-state Engine in one process (one warm-up and three runs each, no waves) and times the hip.select_slots launch alone")
 ap.add_argument("--admit", default="", help="R,n: the whole admission step — R running rows behind 560 .. 1100 positions plus one admitted n-token row: "
                                             "LlamaModel.step_segments against extend(lengths=[0] * R + [n]) followed by a decode_step, alternating")
 ap.add_argument("--prefix-len", type=int, default=576, help="positions of the shared prefix of --share-prefix")
@@ -232,8 +234,8 @@ def serve_e2e(N, K):
     alens = [SERVE_LENGTHS[i % len(SERVE_LENGTHS)] for i in range(N)]
     qs = [torch.randn(n, 4096, device=dev) * 0.02 for n in qlens]
 
-    def engine():
-        eng = serving.Engine(model, K, P + max(qlens) + max(alens), eos_token_id=None, repetition_penalty=1.5)
+    def engine(state=args.state):
+        eng = serving.Engine(model, K, P + max(qlens) + max(alens), eos_token_id=None, repetition_penalty=1.5, **({"state": state} if state != "host" else {}))
         for q, n in zip(qs, alens):
             eng.submit(q, prefix=prefix, max_new_tokens=n)
         out = eng.run()
@@ -250,6 +252,8 @@ def serve_e2e(N, K):
                 mask[i, :q.shape[0]] = 1
             model.generate(inputs_embeds=emb, attention_mask=mask, batching="ragged", prefix_cache=prefix, max_new_tokens=n_new, eos_token_id=None,
                            repetition_penalty=1.5)
+    if args.state == "both":
+        return serve_states(N, K, P, alens, engine)
     res, steps = {}, None
     for name, f in (("engine", engine), ("waves", waves)) * 3:
         torch.cuda.synchronize()
@@ -264,6 +268,41 @@ def serve_e2e(N, K):
         extra = f"{steps['segments']} admission + {steps['decode']} decode steps" if name == "engine" else f"{wave_steps} decode steps in {-(-N // K)} waves"
         print(f"{N} questions over {K} slots behind a {P}-token prefix, answers {','.join(map(str, alens))} ({sum(alens)} tokens), weights {args.weights} [{name}]: "
               f"{t * 1e3:.1f} ms = {sum(alens) / t:.1f} useful tok/s, {extra} (runs {' '.join(f'{x * 1e3:.1f}' for x in ts)})", flush=True)
+
+
+def serve_states(N, K, P, alens, engine):
+    """the host-state against the device-state Engine on the same requests: alternating, one warm-up and three runs each; then the select_slots launch alone
+    (K slots, a 32000-column row each, 64 ids of history, repetition penalty 1.5) in 3 blocks of 50 launches between events"""
+    res, steps = {}, {}
+    for state in ("host", "device") * 4:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        steps[state] = engine(state)
+        torch.cuda.synchronize()
+        res.setdefault(state, []).append(time.perf_counter() - t0)
+    for state, ts in res.items():
+        t = sorted(ts[1:])[1]
+        print(f"{N} questions over {K} slots behind a {P}-token prefix, answers {','.join(map(str, alens))} ({sum(alens)} tokens), weights {args.weights} "
+              f"[engine state={state}]: median {t * 1e3:.1f} ms = {sum(alens) / t:.1f} useful tok/s, {steps[state]['segments']} admission + "
+              f"{steps[state]['decode']} decode steps (warm-up {ts[0] * 1e3:.1f}, runs {' '.join(f'{x * 1e3:.1f}' for x in ts[1:])})", flush=True)
+    V, n_gen = 32000, 64
+    logits = torch.randn(K, V, device=dev) * 4
+    src = torch.arange(K, dtype=torch.int32, device=dev)
+    ids = torch.randint(0, V, (K, max(alens)), device=dev).to(torch.int32)
+    state0 = torch.tensor([[1, n_gen, 10 ** 6, 0]] * K, dtype=torch.int32, device=dev)
+    us = []
+    for _ in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        st = state0.clone()
+        e0.record()
+        for _ in range(50):
+            hip.select_slots(logits, src, st, ids, penalty=1.5)
+            st[:, 1] = n_gen                       # (one tiny fill per launch keeps every launch at the same history length)
+        e1.record()
+        e1.synchronize()
+        us.append(e0.elapsed_time(e1) / 50 * 1e3)
+    print(f"select_slots launch alone (greedy, {K} slots, V {V}, n_gen {n_gen}, + one 4-byte-per-slot fill): {sorted(us)[1]:.1f} us "
+          f"(blocks {' '.join(f'{x:.1f}' for x in us)})", flush=True)
 
 
 def admit_step(R, n):
