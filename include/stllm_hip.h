@@ -642,6 +642,34 @@ int stllm_kv_append_segments(int dtype, const void* src, int64_t ld_src, void* c
                              int max_n, int hidden, int max_len, void* stream);
 
 /*
+ * stllm_attention_segments on a SHARED BASE (additive to ABI 7; always causal): the R segments of a packed query buffer all sit behind the same
+ * P prefix keys — ONE row of a base buffer (kp / vp, row strides kp_rs / vp_rs) that is only read — and each reads its own suffix keys in row slot[r] of the
+ * slot buffers (ks / vs, (slot, row) strides).  The four int32 [R] device tables are those of stllm_attention_segments in SUFFIX-LOCAL positions:
+ *   slot[r], row0[r]   as there
+ *   sfx_off[r]         suffix positions held before this step (0: a fresh admission)
+ *   sfx_len[r]         the suffix end after the append: n_r = sfx_len[r] - sfx_off[r] new rows; clamped as there (sfx_len to [0, max_sfx], sfx_off to
+ *                      [0, sfx_len], n_r to [0, max_n])
+ * Query row i < n_r of segment r is packed row row0[r] + i; it sees all P prefix keys and the suffix keys j <= sfx_off[r] + i of slot row slot[r].
+ * The table guard is stllm_attention_segments': a segment with slot[r] outside [0, n_slots), row0[r] < 0, row0[r] + n_r > T or n_r <= 0 does nothing at all.
+ * bf16 / fp16 at head_dim 128: three launches, no atomics, flags or polling — the prefix as one non-causal problem of T query rows and P keys planned at
+ * (1, H, T, P), the suffixes per segment planned at (R, H, max_n, max_sfx), both leaving (O, m, l) records in the workspace, and a merge that folds a row's
+ * prefix records, then its suffix records, ascending.  With slot[r] = r, row0[r] = r * n, every sfx_off[r] = off and n_r = n the output is bit-identical to
+ * stllm_attention_shared(B = R, G = 1, Sq = n, causal = 1, sfx_q_off = off) on the same buffers.  fp32 at head_dim 128: one vector kernel (no workspace).
+ * Anything else returns STLLM_ERR_UNSUPPORTED.  stllm_last_kernel() is "attn_segments_shared".
+ * workspace: >= stllm_attention_segments_shared_workspace_bytes(R, H, T, P, max_n, max_sfx) bytes (a pure function of the two plans; -1 for an empty
+ * problem), 16-byte aligned, no initialisation needed (unused in fp32).
+ * Memory regions.  Never read: base rows at or behind P; suffix K / V at or behind sfx_len[r]; slot rows named by no live segment; packed q rows at or behind
+ * T.  (The prefix pass reads all T packed q rows, whichever segment owns them.)  Written: exactly the packed out rows row0[r] + i, i < n_r, of live
+ * segments, at columns [0, H * 128).  Every record the merge reads was written by the two passes of the same call.
+ */
+int64_t stllm_attention_segments_shared_workspace_bytes(int R, int H, int T, int P, int max_n, int max_sfx);
+int stllm_attention_segments_shared(int dtype, const void* q, int64_t q_rs, const void* kp, int64_t kp_rs, const void* vp, int64_t vp_rs, int P,
+                                    const void* ks, int64_t ks_bs, int64_t ks_rs, const void* vs, int64_t vs_bs, int64_t vs_rs, void* out,
+                                    int64_t o_rs, int R, int H, int D, int T, int n_slots, int max_n, int max_sfx, float scale,
+                                    const int32_t* slot, const int32_t* row0, const int32_t* sfx_off, const int32_t* sfx_len, void* workspace,
+                                    int64_t workspace_bytes, void* stream);
+
+/*
  * Row gather (token-block assembly, dynamic masking, residual-index selection, embedding lookup):
  *   dst[i, :] = scale * ((idx_a[i] >= 0 ? src_a[idx_a[i], :] : src_b[-idx_a[i]-1, :]) + (add ? add[idx_add[i], :] : 0))
  * all f32, D % 4 == 0.  The same kernel re-orders tokens between the BT-Adapter's spatial '(b t) p' and temporal

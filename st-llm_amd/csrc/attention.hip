@@ -2544,7 +2544,195 @@ int launch_shared(SharedParams p, float scale, float* ws, hipStream_t stream) {
   return STLLM_OK;
 }
 
+// =====================================================================================================
+// Packed segments on a shared base: the R segments of stllm_attention_segments, every one of them behind the SAME P prefix keys — ONE row of a
+// base buffer that is never written — and its own suffix keys in row slot[r] of the slot buffers.  The tables are suffix-local (q_off_tab = sfx_off, kv_len = sfx_len).
+//   16-bit: the extend scheme of launch_shared on a packed buffer, three launches — the prefix as ONE non-causal problem of T query rows and P keys
+//     (attn_mfma_kernel<T, 128, NW, SPLIT>, full query tiles whatever the segments' lengths), the suffixes per segment (the SEG + SPLIT + LIVE instantiation of
+//     stllm_attention_segments' key split, which always leaves records here) and attn_segments_shared_merge_kernel.
+//   fp32: attn_segments_shared_f32_kernel, attn_shared_f32_kernel's two-source key loop addressed through the segment tables.
+// Both new kernels take seg_row's guard first: a pad row or a bad segment returns before it reads a record or a key and writes nothing.
+// =====================================================================================================
+struct SegSharedParams {
+  AttnSegParams seg;                    // q / o (packed), ks / vs as k / v, the four tables, T, n_slots, B = R, Sq = max_n, Skv = max_sfx, ws = suffix records, nsplit = their count
+  const char* kp; int64_t kp_rs;        // the ONE prefix row
+  const char* vp; int64_t vp_rs;
+  int P;
+  const float* ws_p; int n_p;           // prefix records [H][T][n_p]
+  float m_mult;                         // merge: log2-domain maximum = record maximum * m_mult (the records keep RAW maxima)
+};
+
+// one workgroup (one wave) per (query row i, head, segment r): attn_shared_merge_kernel's fold — the n_p prefix records of packed row row0[r] + i, then the
+// n_s suffix records of (r, i), ascending — in the same arithmetic and the same order
+template <typename T>
+__global__ __launch_bounds__(64) void attn_segments_shared_merge_kernel(const SegSharedParams p) {
+  const int lane = threadIdx.x, i = blockIdx.x, h = blockIdx.y, r = blockIdx.z;
+  const SegRow s = seg_row(p.seg, r);
+  if (i >= s.n) return;
+  const int n_p = p.n_p, n_s = p.seg.nsplit;
+  const int64_t row = (int64_t)s.row0 + i;
+  const float* ra = p.ws_p + (((int64_t)h * p.seg.T + row) * n_p) * kSplRec;
+  const float* rb = p.seg.ws + ((((int64_t)r * p.seg.H + h) * p.seg.Sq + i) * n_s) * kSplRec;
+  float mm = kNeg * 2.0f;
+  for (int c = 0; c < n_p; ++c) mm = fmaxf(mm, ra[c * kSplRec + 128] * p.m_mult);
+  for (int c = 0; c < n_s; ++c) mm = fmaxf(mm, rb[c * kSplRec + 128] * p.m_mult);
+  float ll = 0.0f, a0 = 0.0f, a1 = 0.0f;
+  for (int c = 0; c < n_p; ++c) {
+    const float f = __builtin_amdgcn_exp2f(ra[c * kSplRec + 128] * p.m_mult - mm);   // empty records: exp2(-huge) == 0
+    ll = fmaf(ra[c * kSplRec + 129], f, ll);
+    a0 = fmaf(ra[c * kSplRec + 2 * lane], f, a0);
+    a1 = fmaf(ra[c * kSplRec + 2 * lane + 1], f, a1);
+  }
+  for (int c = 0; c < n_s; ++c) {
+    const float f = __builtin_amdgcn_exp2f(rb[c * kSplRec + 128] * p.m_mult - mm);
+    ll = fmaf(rb[c * kSplRec + 129], f, ll);
+    a0 = fmaf(rb[c * kSplRec + 2 * lane], f, a0);
+    a1 = fmaf(rb[c * kSplRec + 2 * lane + 1], f, a1);
+  }
+  const float inv = 1.0f / ll;
+  uint32_t* op = reinterpret_cast<uint32_t*>(p.seg.o + (row * p.seg.o_rs + (int64_t)h * kDecD + 2 * lane) * 2);
+  *op = Elem<T>::pack2(a0 * inv, a1 * inv);
+}
+
+// fp32 (the verify mode): one workgroup per (i, h, r); wave w takes keys w, w + 4, ... of the P prefix keys and the suffix keys j <= sfx_off + i (prefix first)
+__global__ __launch_bounds__(256) void attn_segments_shared_f32_kernel(const SegSharedParams p) {
+  __shared__ float part[4][kSplRec];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x, h = blockIdx.y, r = blockIdx.z;
+  const SegRow s = seg_row(p.seg, r);
+  if (i >= s.n) return;   // workgroup-uniform: nobody waits at the barrier below
+  const int ns = min(s.kvlen, s.q_off + i + 1);
+  const int64_t row = (int64_t)s.row0 + i;
+  const f32x2 qv = *reinterpret_cast<const f32x2*>(reinterpret_cast<const float*>(p.seg.q) + row * p.seg.q_rs + (int64_t)h * kDecD + 2 * lane);
+  const float q0 = qv[0] * p.seg.scale_log2, q1 = qv[1] * p.seg.scale_log2;
+  const float* kpf = reinterpret_cast<const float*>(p.kp) + (int64_t)h * kDecD + 2 * lane;
+  const float* vpf = reinterpret_cast<const float*>(p.vp) + (int64_t)h * kDecD + 2 * lane;
+  const float* ksf = reinterpret_cast<const float*>(p.seg.k) + (int64_t)s.slot * p.seg.k_bs + (int64_t)h * kDecD + 2 * lane;
+  const float* vsf = reinterpret_cast<const float*>(p.seg.v) + (int64_t)s.slot * p.seg.v_bs + (int64_t)h * kDecD + 2 * lane;
+  float m = kNeg, l = 0.0f, o0 = 0.0f, o1 = 0.0f;
+  const int total = p.P + ns;
+  for (int j = wave; j < total; j += 4) {
+    const bool pre = j < p.P;
+    const f32x2 kk = *reinterpret_cast<const f32x2*>(pre ? kpf + (int64_t)j * p.kp_rs : ksf + (int64_t)(j - p.P) * p.seg.k_rs);
+    const f32x2 vv = *reinterpret_cast<const f32x2*>(pre ? vpf + (int64_t)j * p.vp_rs : vsf + (int64_t)(j - p.P) * p.seg.v_rs);
+    const float sc = wave_sum(fmaf(q0, kk[0], q1 * kk[1]));
+    const float mn = fmaxf(m, sc);
+    const float alpha = __builtin_amdgcn_exp2f(m - mn), pr = __builtin_amdgcn_exp2f(sc - mn);
+    l = fmaf(l, alpha, pr);
+    o0 = fmaf(o0, alpha, pr * vv[0]);
+    o1 = fmaf(o1, alpha, pr * vv[1]);
+    m = mn;
+  }
+  if (lane == 0) { part[wave][128] = m; part[wave][129] = l; }
+  part[wave][2 * lane] = o0;
+  part[wave][2 * lane + 1] = o1;
+  __syncthreads();
+  if (wave == 0) {
+    const float mm = fmaxf(fmaxf(part[0][128], part[1][128]), fmaxf(part[2][128], part[3][128]));
+    float ll = 0.0f, a0 = 0.0f, a1 = 0.0f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float f = __builtin_amdgcn_exp2f(part[w][128] - mm);
+      ll = fmaf(part[w][129], f, ll);
+      a0 = fmaf(part[w][2 * lane], f, a0);
+      a1 = fmaf(part[w][2 * lane + 1], f, a1);
+    }
+    const f32x2 res = {a0 / ll, a1 / ll};
+    *reinterpret_cast<f32x2*>(reinterpret_cast<float*>(p.seg.o) + row * p.seg.o_rs + (int64_t)h * kDecD + 2 * lane) = res;
+  }
+}
+
+// the suffix pass: launch_ksplit's partial launch on the SEG instantiation, without its merge
+template <typename T>
+void launch_segments_shared_suffix(AttnSegParams s, const KsplitPlan& pl, hipStream_t stream) {
+  s.nsplit = pl.nsplit;
+  s.kps = pl.kps;
+  switch (pl.nw) {
+    case 1: launch_ksplit_nw<T, 1, true, true>(s, pl, stream); break;
+    case 2: launch_ksplit_nw<T, 2, true, true>(s, pl, stream); break;
+    case 3: launch_ksplit_nw<T, 3, true, true>(s, pl, stream); break;
+    default: launch_ksplit_nw<T, 4, true, true>(s, pl, stream); break;
+  }
+}
+
+template <typename T>
+int launch_segments_shared(SegSharedParams p, float* ws, hipStream_t stream) {
+  const AttnSegParams& g = p.seg;
+  const KsplitPlan pa = ksplit_plan(1, g.H, g.T, p.P), pb = ksplit_plan(g.B, g.H, g.Sq, g.Skv);
+  float* ws_p = ws;
+  float* ws_s = ws + (int64_t)g.H * g.T * pa.nsplit * kSplRec;
+  AttnParams a{};
+  a.q = g.q; a.q_bs = 0; a.q_rs = g.q_rs;                  // the T packed rows are ONE batch row of query rows
+  a.k = p.kp; a.k_bs = 0; a.k_rs = p.kp_rs;
+  a.v = p.vp; a.v_bs = 0; a.v_rs = p.vp_rs;
+  a.B = 1; a.H = g.H; a.Sq = g.T; a.Skv = p.P; a.D = kDecD;   // Skv = P: key rows at or behind P are not loaded
+  a.scale = g.scale; a.scale_log2 = g.scale_log2;
+  a.ws = ws_p;
+  launch_shared_pass<T, false>(a, pa, stream);
+  STLLM_CHECK_LAUNCH("stllm_attention_segments_shared(prefix pass)");
+  p.seg.ws = ws_s;
+  launch_segments_shared_suffix<T>(p.seg, pb, stream);
+  STLLM_CHECK_LAUNCH("stllm_attention_segments_shared(suffix pass)");
+  p.seg.nsplit = pb.nsplit;
+  p.ws_p = ws_p; p.n_p = pa.nsplit;
+  p.m_mult = g.scale_log2;
+  hipLaunchKernelGGL(attn_segments_shared_merge_kernel<T>, dim3(g.Sq, g.H, g.B), dim3(64), 0, stream, p);
+  STLLM_CHECK_LAUNCH("stllm_attention_segments_shared(merge)");
+  stllm_set_last_kernel("attn_segments_shared");
+  return STLLM_OK;
+}
+
 }  // namespace
+
+extern "C" int64_t stllm_attention_segments_shared_workspace_bytes(int R, int H, int T, int P, int max_n, int max_sfx) {
+  if (R <= 0 || H <= 0 || T <= 0 || P <= 0 || max_n <= 0 || max_sfx <= 0) return -1;
+  return ((int64_t)H * T * ksplit_plan(1, H, T, P).nsplit + (int64_t)R * H * max_n * ksplit_plan(R, H, max_n, max_sfx).nsplit) * kSplRec * 4;
+}
+
+extern "C" int stllm_attention_segments_shared(int dtype, const void* q, int64_t q_rs, const void* kp, int64_t kp_rs, const void* vp, int64_t vp_rs, int P,
+                                               const void* ks, int64_t ks_bs, int64_t ks_rs, const void* vs, int64_t vs_bs, int64_t vs_rs, void* out,
+                                               int64_t o_rs, int R, int H, int D, int T, int n_slots, int max_n, int max_sfx, float scale,
+                                               const int32_t* slot, const int32_t* row0, const int32_t* sfx_off, const int32_t* sfx_len, void* workspace,
+                                               int64_t workspace_bytes, void* stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  STLLM_CHECK_ARG(q && kp && vp && ks && vs && out && slot && row0 && sfx_off && sfx_len, "stllm_attention_segments_shared: null pointer");
+  STLLM_CHECK_ARG(R > 0 && R <= 65535 && H > 0 && T > 0 && P > 0 && n_slots > 0 && max_n > 0 && max_sfx > 0,
+                  "stllm_attention_segments_shared: empty problem (or R > 65535) (R %d, H %d, T %d, P %d, n_slots %d, max_n %d, max_sfx %d)",
+                  R, H, T, P, n_slots, max_n, max_sfx);
+  if (D != kDecD || (dtype != STLLM_BF16 && dtype != STLLM_F16 && dtype != STLLM_F32)) {
+    stllm_set_error("stllm_attention_segments_shared: head_dim %d / dtype %d unsupported (bf16 / fp16 / fp32 at head_dim 128)", D, dtype);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  STLLM_CHECK_ARG(aligned16(q) && aligned16(kp) && aligned16(vp) && aligned16(ks) && aligned16(vs) && aligned16(out),
+                  "stllm_attention_segments_shared: pointers must be 16-byte aligned");
+  STLLM_CHECK_ARG(q_rs % 8 == 0 && kp_rs % 8 == 0 && vp_rs % 8 == 0 && ks_bs % 8 == 0 && ks_rs % 8 == 0 && vs_bs % 8 == 0 && vs_rs % 8 == 0 && o_rs % 8 == 0,
+                  "stllm_attention_segments_shared: strides must be multiples of 8 elements");
+  STLLM_CHECK_ARG(((reinterpret_cast<uintptr_t>(slot) | reinterpret_cast<uintptr_t>(row0) | reinterpret_cast<uintptr_t>(sfx_off) |
+                    reinterpret_cast<uintptr_t>(sfx_len)) & 3) == 0, "stllm_attention_segments_shared: tables must be 4-byte aligned");
+  SegSharedParams p{};
+  AttnSegParams& g = p.seg;
+  g.q = (const char*)q; g.q_bs = 0; g.q_rs = q_rs;
+  g.k = (const char*)ks; g.k_bs = ks_bs; g.k_rs = ks_rs;
+  g.v = (const char*)vs; g.v_bs = vs_bs; g.v_rs = vs_rs;
+  g.o = (char*)out; g.o_bs = 0; g.o_rs = o_rs;
+  g.B = R; g.H = H; g.Sq = max_n; g.Skv = max_sfx; g.D = D;
+  g.scale = scale; g.scale_log2 = scale * 1.44269504088896340736f;
+  g.causal = 1; g.kv_len = sfx_len; g.q_off_tab = sfx_off;
+  g.slot = slot; g.row0 = row0; g.T = T; g.n_slots = n_slots;
+  p.kp = (const char*)kp; p.kp_rs = kp_rs;
+  p.vp = (const char*)vp; p.vp_rs = vp_rs;
+  p.P = P;
+  if (dtype == STLLM_F32) {
+    hipLaunchKernelGGL(attn_segments_shared_f32_kernel, dim3(max_n, H, R), dim3(256), 0, stream, p);
+    STLLM_CHECK_LAUNCH("stllm_attention_segments_shared(fp32)");
+    stllm_set_last_kernel("attn_segments_shared");
+    return STLLM_OK;
+  }
+  STLLM_CHECK_ARG(workspace && aligned16(workspace) && workspace_bytes >= stllm_attention_segments_shared_workspace_bytes(R, H, T, P, max_n, max_sfx),
+                  "stllm_attention_segments_shared: workspace too small or misaligned");
+  float* ws = reinterpret_cast<float*>(workspace);
+  return dtype == STLLM_BF16 ? launch_segments_shared<bf16_t>(p, ws, stream) : launch_segments_shared<f16_t>(p, ws, stream);
+}
 
 extern "C" int64_t stllm_attention_shared_workspace_bytes(int B, int G, int H, int Sq, int P, int max_sfx) {
   if (B <= 0 || G <= 0 || B % G != 0 || H <= 0 || Sq <= 0 || P <= 0 || max_sfx <= 0) return -1;

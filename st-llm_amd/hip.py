@@ -31,7 +31,8 @@ EXPORTS = ["stllm_last_error", "stllm_abi_version", "stllm_last_kernel", "stllm_
            "stllm_attention_decode_ragged_workspace_bytes", "stllm_attention_decode_ragged", "stllm_kv_append_rows",
            "stllm_attention_shared_workspace_bytes", "stllm_attention_shared", "stllm_select_tokens", "stllm_beam_candidates",
            "stllm_attention_offset_ragged_workspace_bytes", "stllm_attention_offset_ragged", "stllm_kv_append_spans",
-           "stllm_attention_segments_workspace_bytes", "stllm_attention_segments", "stllm_kv_append_segments", "stllm_select_slots"]
+           "stllm_attention_segments_workspace_bytes", "stllm_attention_segments", "stllm_kv_append_segments", "stllm_select_slots",
+           "stllm_attention_segments_shared_workspace_bytes", "stllm_attention_segments_shared"]
 
 
 def torch_dtype(d):
@@ -220,6 +221,9 @@ def _bind(L, strict=True):
     B("stllm_attention_segments", [c_int, c_void_p, c_int64] + [c_void_p, c_int64, c_int64] * 2 + [c_void_p, c_int64] + [c_int] * 7 + [c_float] + [c_void_p] * 5 +
       [c_int64, c_void_p])
     B("stllm_kv_append_segments", [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64] + [c_void_p] * 4 + [c_int] * 6 + [c_void_p])
+    B("stllm_attention_segments_shared_workspace_bytes", [c_int] * 6, c_int64)
+    B("stllm_attention_segments_shared", [c_int] + [c_void_p, c_int64] * 3 + [c_int] + [c_void_p, c_int64, c_int64] * 2 + [c_void_p, c_int64] + [c_int] * 7 +
+      [c_float] + [c_void_p] * 5 + [c_int64, c_void_p])
     B("stllm_attention_offset", [c_int] + [c_void_p, c_int64, c_int64] * 4 + [c_int] * 5 + [c_float, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_llama_layers_extend", [ctypes.POINTER(LlamaLayersArgs), ctypes.POINTER(LlamaLayerWeights), c_int, c_int, c_void_p, c_int64, c_void_p])
     B("stllm_gemv_w8", [ctypes.POINTER(GemvW8Args), c_void_p])
@@ -1121,6 +1125,43 @@ def attention_segments(q, k, v, slot, row0, q_off, kv_len, *, H, D, T, n_slots, 
     _check(lib().stllm_attention_segments(dtype_code(td), _p(q), q.stride(0), _p(k), ks[0], ks[1], _p(v), vs[0], vs[1], _p(out), out.stride(0),
                                           R, H, D, T, n_slots, max_n, max_kv, scale, _p(slot), _p(row0), _p(q_off), _p(kv_len),
                                           _p(ws), ws.numel() if ws is not None else 0, _stream()), "stllm_attention_segments")
+    return out
+
+
+def segments_shared_available(device):
+    """attention_segments_shared (and kv_append_segments) can serve tensors on `device`: a device check, nothing more (as segments_available).
+    LlamaModel.step_segments asks before anything is written on a cache with a base; a stand-in for this module that states the contract answers for itself."""
+    return torch.device(device).type == "cuda"
+
+
+def attention_segments_shared(q, kp, vp, ks, vs, slot, row0, sfx_off, sfx_len, *, H, D, T, P, n_slots, max_n, max_sfx, scale, out=None, kp_strides=None,
+                              ks_strides=None):
+    """stllm_attention_segments_shared: attention_segments for segments that all sit behind the same P prefix keys.  q: 2-D view of T packed rows; kp / vp: 2-D
+    views of the ONE base row (kp_strides: its (batch, row) strides, of which only the row stride is used; never written); ks / vs: 2-D views of the slot
+    buffers, ks_strides their (slot, row) strides; slot, row0, sfx_off, sfx_len: int32 [R] on the device in SUFFIX-LOCAL positions — segment r holds
+    sfx_off[r] suffix positions and n_r = sfx_len[r] - sfx_off[r] (<= max_n) new ones; its row i sees the P prefix keys and the suffix keys
+    j <= sfx_off[r] + i.  Only the packed rows of live segments are written (out: [T, H * D]).  bf16 / fp16 / fp32 at D = 128; anything else is an error
+    (STLLM_ERR_UNSUPPORTED), not a fallback.  The record workspace comes from the per-(device, stream) scratch cache (split_workspace)."""
+    td = q.dtype
+    R = slot.numel()
+    for t, what in ((slot, "slot"), (row0, "row0"), (sfx_off, "sfx_off"), (sfx_len, "sfx_len")):
+        _req(t, torch.int32, what)
+        if t.numel() != R:
+            raise RuntimeError(f"attention_segments_shared: {what} has {t.numel()} entries for R = {R}")
+    if q.shape[0] < T or (out is not None and out.shape[0] < T):
+        raise RuntimeError(f"attention_segments_shared: q {tuple(q.shape)} / out {None if out is None else tuple(out.shape)} hold fewer than T = {T} rows")
+    kps = kp_strides if kp_strides is not None else (P * kp.stride(0), kp.stride(0))
+    kss = ks_strides if ks_strides is not None else (max_sfx * ks.stride(0), ks.stride(0))
+    if out is None:
+        out = torch.empty((T, H * D), device=q.device, dtype=td)
+    need = int(lib().stllm_attention_segments_shared_workspace_bytes(R, H, T, P, max_n, max_sfx))
+    if need < 0:
+        raise RuntimeError(f"stllm_attention_segments_shared_workspace_bytes: bad shape (R={R}, H={H}, T={T}, P={P}, max_n={max_n}, max_sfx={max_sfx})")
+    ws = split_workspace(q.device, need) if td != torch.float32 else None
+    _check(lib().stllm_attention_segments_shared(dtype_code(td), _p(q), q.stride(0), _p(kp), kps[1], _p(vp), kps[1], P, _p(ks), kss[0], kss[1],
+                                                 _p(vs), kss[0], kss[1], _p(out), out.stride(0), R, H, D, T, n_slots, max_n, max_sfx, scale,
+                                                 _p(slot), _p(row0), _p(sfx_off), _p(sfx_len), _p(ws), ws.numel() if ws is not None else 0, _stream()),
+           "stllm_attention_segments_shared")
     return out
 
 

@@ -254,10 +254,11 @@ class KVCache:
         self.set_lens(lens)
 
     def release(self, slot):
-        """row `slot` holds nothing any more (its bytes are don't-care from here on); every other row is left alone"""
-        assert 0 <= slot < self.batch and self.base is None
+        """row `slot` holds nothing any more (its bytes are don't-care from here on); every other row is left alone.  On a cache with a base the row goes
+        back to the base's positions: its own suffix is what it forgets."""
+        assert 0 <= slot < self.batch
         lens = self.row_lens()
-        lens[slot] = 0
+        lens[slot] = self.base_len
         self.truncate(lens)
 
     def truncate(self, n):
@@ -575,19 +576,20 @@ class LlamaModel(nn.Module):
         scratch (RoPE rows gathered at lens[slot] + i, rope_seq = T) -> hip.kv_append_segments -> hip.attention_segments -> o_proj -> MLP.  No pad rows
         anywhere: T GEMM rows, T query rows.  Sets the length of every named slot to lens + n; a slot that is not named keeps its length and its bytes.
         Returns the final-norm hidden rows of every segment's LAST token only: (f32 [R, D], compute dtype [R, D]).  bf16 / fp16 / fp32; the split
-        modes, a cache with a base and quantised decode weights raise (the quantised modes serve pure-decode steps through decode_step)."""
+        modes and quantised decode weights raise (the quantised modes serve pure-decode steps through decode_step).  A cache with a base (one base row)
+        takes step_segments_shared: the same contract, the base's K / V read once for all packed rows."""
         cfg = self.config
         dt = runtime.compute_dtype()
         if runtime.gemm_split():
             raise NotImplementedError("LlamaModel.step_segments runs in the bf16 / fp16 / fp32 modes; the bf16x3 / mixed modes have no segment path")
         if runtime.decode_weights() is not None:
             raise NotImplementedError(f"LlamaModel.step_segments streams the 16-bit weights: {runtime.decode_weights()} decode weights serve decode_step only")
-        if cache.base is not None:
-            raise NotImplementedError("LlamaModel.step_segments on a KV cache with a shared base: fork() it first")
         T, D = embeds.shape
         H = cfg.num_attention_heads
         hd = D // H
         dev = embeds.device
+        if cache.base is not None:
+            return self.step_segments_shared(embeds, cache, segments)
         if not hip.segments_available(dev):
             raise NotImplementedError("LlamaModel.step_segments needs hip.attention_segments / hip.kv_append_segments, which this backend does not provide for " +
                                       str(dev))
@@ -618,6 +620,61 @@ class LlamaModel(nn.Module):
             k, v, _ = cache.kv(li)
             return hip.attention_segments(dense[:, :D], k, v, slot_t, row0_t, q_off, kv_len, H=H, D=hd, T=T, n_slots=cache.batch, max_n=max_n, max_kv=max_kv,
                                           scale=hd ** -0.5, k_strides=strides, v_strides=strides)
+        proj = gemm_proj(layers, dt, True)
+        for li, pk in enumerate(layers):
+            decoder_layer(self, dt, x, pk, li, proj=proj, qkv_to=lambda li: {"out": dense}, attn=attn, rope=(cos, sin), rope_seq=T)
+        for s, p, n in zip(slots, have, new):
+            lens[s] = p + n
+        cache.set_lens(lens)
+        last = hip.gather_rows(x, tab([r0 + n - 1 for r0, n in zip(row0, new)]))
+        h16, h32 = hip.rmsnorm(last, self.norm.weight, cfg.rms_norm_eps, dtype=dt, want_f32=True)
+        return h32, h16
+
+    def step_segments_shared(self, embeds, cache, segments):
+        """step_segments on a cache with a shared base (KVCache.share of ONE base row; reached through step_segments, which has checked the
+        modes): the same contract.  RoPE rows are gathered at the TOTAL positions lens[slot] + i; the append and the attention work on the cache's own
+        [slots, max_len - P, 3D] buffers at the LOCAL positions lens[slot] - P — hip.kv_append_segments, then hip.attention_segments_shared, which reads the
+        base's P keys once for all T packed rows and every segment's own suffix.  The base's buffers are only read."""
+        cfg = self.config
+        dt = runtime.compute_dtype()
+        T, D = embeds.shape
+        H = cfg.num_attention_heads
+        hd = D // H
+        dev = embeds.device
+        P = cache.base_len
+        if cache.base.batch != 1:
+            raise NotImplementedError(f"LlamaModel.step_segments on a KV cache with a shared base of {cache.base.batch} rows: one base row (one video) only; "
+                                      "fork() it first")
+        if not hip.segments_shared_available(dev):
+            raise NotImplementedError("LlamaModel.step_segments on a KV cache with a shared base needs hip.attention_segments_shared / hip.kv_append_segments, "
+                                      "which this backend does not provide for " + str(dev))
+        segments = [(int(s), int(n)) for s, n in segments]
+        slots, new = [s for s, _ in segments], [n for _, n in segments]
+        assert segments and len(set(slots)) == len(slots) and all(0 <= s < cache.batch for s in slots), "step_segments: slots must be distinct and in range"
+        assert min(new) >= 1 and sum(new) == T, "step_segments: every segment carries at least one token and the segments cover the packed rows"
+        assert cache.qkv[0].dtype == dt and cache.base.qkv[0].dtype == dt
+        lens = cache.row_lens()
+        have = [lens[s] for s in slots]
+        assert all(p + n <= cache.max_len for p, n in zip(have, new)), "KV cache full"
+        row0 = [sum(new[:r]) for r in range(len(new))]
+        layers = self.pack(dt)
+        x = embeds.float().clone()
+        cos, sin = self.rope(cache.max_len, dev)
+
+        def tab(v):
+            return hip.h2d(torch.tensor(v, dtype=torch.int32), dev)
+        pos = tab([p + i for p, n in zip(have, new) for i in range(n)])
+        cos, sin = hip.gather_rows(cos, pos), hip.gather_rows(sin, pos)
+        off = [p - P for p in have]                                   # suffix-local from here on
+        slot_t, row0_t, sfx_off, n_new, sfx_len = tab(slots), tab(row0), tab(off), tab(new), tab([p + n for p, n in zip(off, new)])
+        max_n, max_sfx = max(new), max(p + n for p, n in zip(off, new))
+        dense = torch.empty((T, 3 * D), device=dev, dtype=dt)
+
+        def attn(li, dense):
+            hip.kv_append_segments(dense, cache.qkv[li], slot_t, row0_t, sfx_off, n_new, T=T, max_n=max_n)
+            (kp, vp, kp_strides), (ks, vs, ks_strides) = cache.base.kv(li), cache.kv(li)
+            return hip.attention_segments_shared(dense[:, :D], kp, vp, ks, vs, slot_t, row0_t, sfx_off, sfx_len, H=H, D=hd, T=T, P=P, n_slots=cache.batch,
+                                                 max_n=max_n, max_sfx=max_sfx, scale=hd ** -0.5, kp_strides=kp_strides, ks_strides=ks_strides)
         proj = gemm_proj(layers, dt, True)
         for li, pk in enumerate(layers):
             decoder_layer(self, dt, x, pk, li, proj=proj, qkv_to=lambda li: {"out": dense}, attn=attn, rope=(cos, sin), rope_seq=T)

@@ -7,7 +7,7 @@ batch.  The Engine owns one KVCache of `slots` rows instead.  Every step it free
   * a step WITH admissions is LlamaModel.step_segments: the step's tokens packed as [T, D] — one token for every running request, the whole remaining
     prompt of every admitted one — on hip.kv_append_segments / hip.attention_segments.  No pad rows; running rows do not stall.
   * a step WITHOUT admissions is LlamaModel.decode_step on the slot cache, the GEMV path that a fixed batch takes (quantised decode weights included).
-    Free slots ride along as don't-care rows; their length is put back to 0 afterwards.
+    Free slots ride along as don't-care rows; their length is put back to 0 (with a base: to the base's length) afterwards.
 
 Selection is per request, with generate()'s own processors (generation._process_logits / _warp_logits) on that request's ids and step count: a request
 generates the ids that generate() gives for it alone (greedy; sampling with its own generator).
@@ -17,9 +17,14 @@ generated ids [slots, max_new] and the stop sequences.  ONE hip.select_slots lau
 appends the token and settles whether the request is finished; the next step's embeddings are gathered from the table's `pending` column.  The host reads
 the table once per step, and a request's ids once, when it finishes.  A request generates the ids of generate(selection="device") for it alone.
 
-Not served (they raise): beams, selection="device" among the options (the device path of the Engine is state="device"), share_prefix / caches with a base,
-return_cache; with state="device" also stopping_criteria (Python callables need the ids on the host) and sync_every != 1.  No paged blocks, no preemption:
-a request must fit `max_len` positions when it is submitted and keeps its slot until it finishes."""
+Engine(base=prefix) serves many questions about ONE prefilled video without copying it: the slot cache is prefix.share(rows=slots, ...), every
+slot holds only the positions behind the prefix, an admission copies nothing, a step with admissions runs hip.attention_segments_shared (the prefix's K / V read
+once for all packed rows) and a step without runs decode_step's shared-prefix attention.  A released or idle slot sits at the prefix's length, not at 0.
+
+Not served (they raise): beams, selection="device" among the options (the device path of the Engine is state="device"), generate()'s share_prefix option,
+return_cache, a `prefix` with a base of its own, more than one base per Engine (submit(prefix=) other than the Engine's base); with state="device" also
+stopping_criteria (Python callables need the ids on the host) and sync_every != 1.  No paged blocks, no preemption: a request must fit `max_len` positions
+when it is submitted and keeps its slot until it finishes."""
 import collections
 
 import torch
@@ -40,9 +45,11 @@ class Engine:
     """Engine(lm_wrapper, slots, max_len, **options): `lm_wrapper` is what generate() runs on (`.model` a LlamaModel, `.logits_from`), `options` are
     generate()'s sampling and stopping options (generation.Options); num_beams == 1, use_cache and selection == "torch" only.
     state: "host" (default) selects per request on the host with generate()'s processors; "device" keeps the per-request selection state on the device
-    and selects for all slots in one hip.select_slots launch (see the module docstring)."""
+    and selects for all slots in one hip.select_slots launch (see the module docstring).
+    base: a one-row uniform KVCache without a base of its own (Chat.prefill_video(...).cache) that EVERY request sits behind; it is held by reference and only
+    read.  max_len keeps counting total positions (the base's included)."""
 
-    def __init__(self, lm_wrapper, slots, max_len, device=None, state="host", **options):
+    def __init__(self, lm_wrapper, slots, max_len, device=None, state="host", base=None, **options):
         o = generation.Options(**options)
         if state not in ("host", "device"):
             raise ValueError(f"serving.Engine: state must be 'host' or 'device', got {state!r}")
@@ -59,8 +66,17 @@ class Engine:
         self.m, self.lm = lm_wrapper, lm_wrapper.model
         self.device = torch.device(device) if device is not None else self.lm.embed_tokens.weight.device
         assert slots >= 1 and max_len >= 2
-        self.cache = self.lm.new_cache(slots, max_len, self.device)
-        self.cache.set_lens([0] * slots)
+        self.base = base
+        if base is not None:
+            if base.base is not None or base.lens is not None or base.batch != 1:
+                raise NotImplementedError("serving.Engine(base=): a one-row uniform KVCache without a base")
+            if max_len <= base.len:
+                raise ValueError(f"serving.Engine(base=): max_len {max_len} counts total positions and the base holds {base.len}")
+            assert base.qkv[0].device == self.device, "serving.Engine(base=): the base lives on the Engine's device"
+            self.cache = base.share(rows=slots, max_new=max_len - base.len)    # every row at the base's length; nothing is copied
+        else:
+            self.cache = self.lm.new_cache(slots, max_len, self.device)
+            self.cache.set_lens([0] * slots)
         self.queue = collections.deque()
         self.running = {}                 # slot -> _Request
         self.done_slots = []              # slots whose request finished in the last step: released at the start of the next one
@@ -75,11 +91,17 @@ class Engine:
     def submit(self, inputs_embeds, prefix=None, max_new_tokens=None, generator=None):
         """queue a request: inputs_embeds [S, D] (S >= 1), the prompt — or, with `prefix` (a one-row uniform KVCache without a base, e.g.
         Chat.prefill_video(...).cache, only ever read), what follows the prefix's positions.  generator: the request's own torch.Generator for do_sample
-        (default: the Engine's `generator` option).  Raises if prefix + prompt + max_new_tokens does not fit a slot.  Returns the handle."""
+        (default: the Engine's `generator` option).  Raises if prefix + prompt + max_new_tokens does not fit a slot.  Returns the handle.
+        An Engine with a base: every request sits behind the base; `prefix` is None or that same object, anything else raises ValueError."""
         max_new = self.o.max_new_tokens if max_new_tokens is None else int(max_new_tokens)
         assert inputs_embeds.dim() == 2 and inputs_embeds.shape[0] >= 1 and max_new >= 1
         P = 0
-        if prefix is not None:
+        if self.base is not None:
+            if prefix is not None and prefix is not self.base:
+                raise ValueError("serving.Engine(base=).submit(prefix=): one base per Engine — every request sits behind the Engine's base, so prefix is "
+                                 "None or that same cache")
+            P, prefix = self.base.len, None      # nothing to load at admission: the slot reads the base
+        elif prefix is not None:
             if prefix.base is not None or prefix.lens is not None or prefix.batch != 1:
                 raise NotImplementedError("serving.Engine.submit(prefix=): a one-row uniform KVCache without a base")
             P = prefix.len

@@ -172,6 +172,68 @@ if "--ragged-suffix" in sys.argv:
         print(f"ragged suffix B={B} P={','.join(map(str, Ps))} n={','.join(map(str, ns))}: key-split {fmt('split')}  tile {fmt('tile')}  auto {fmt('auto')} -> {auto}"
               f"  | parent: per-row offset calls {fmt('per-row')}  {S} decode steps {fmt('steps')}", flush=True)
     sys.exit(0)
+if "--segments-shared" in sys.argv:
+    # --segments-shared P (repeatable; default 576 and 2048): the packed admission step of serving.Engine(base=) at the shape of --segments' default case — 15
+    # one-token segments plus one 40-token segment, every segment behind the SAME P prefix keys.  The suffix offsets are those the default case has behind a
+    # 576-token prefix (totals 560 .. 1100; the one-token segments that would sit in front of position 576 are placed at 576: an empty suffix), the 40-token
+    # segment sits behind 4 suffix positions (total 580); a larger P keeps the offsets.
+    #   shared : hip.attention_segments_shared — prefix pass over ONE copy of the prefix (T query rows, full tiles), suffix pass per segment, merge;
+    #   copies : hip.attention_segments on R private copies of prefix + suffix (what KVCache.load_row gives), by the dispatch rule (auto) and with the key
+    #            split forced on.
+    # Same process, alternating, every timing a captured graph of 20 calls; best of 5 replays, every round printed.
+    def timed_h(fn, rounds=5):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(20):
+                fn()
+        g.replay(); torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        best = float("inf")
+        for _ in range(rounds):
+            s.record(); g.replay(); e.record(); torch.cuda.synchronize()
+            best = min(best, s.elapsed_time(e) / 20 * 1e3)
+        return best
+    H, D, dt = 32, 128, torch.bfloat16
+    HD, W = H * D, 3 * H * D
+    Pl = [int(sys.argv[i + 1]) for i, a in enumerate(sys.argv) if a == "--segments-shared" and i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit()]
+    offs = [max(0, 560 + (540 * i) // 14 - 576) for i in range(15)] + [4]
+    ns = [1] * 15 + [40]
+    for P in Pl or [576, 2048]:
+        R, S, T, max_sfx = len(ns), max(ns), sum(ns), max(o + n for o, n in zip(offs, ns))
+        MLp, MLs, MLc = P + 8, max_sfx + 8, P + max_sfx + 8
+        pre = torch.randn(MLp, W, device="cuda").to(dt)
+        suf = torch.randn(R * MLs, W, device="cuda").to(dt)
+        cop = torch.randn(R * MLc, W, device="cuda").to(dt)
+        packed = torch.randn(T, W, device="cuda").to(dt)
+        out = torch.empty(T, HD, device="cuda", dtype=dt)
+        i32 = lambda x: torch.tensor(x, dtype=torch.int32).cuda()
+        row0 = [sum(ns[:r]) for r in range(R)]
+        slot, row0_t, sfx_off, sfx_len = i32(list(range(R))), i32(row0), i32(offs), i32([o + n for o, n in zip(offs, ns)])
+        q_off, kv_len = i32([P + o for o in offs]), i32([P + o + n for o, n in zip(offs, ns)])
+        shared = lambda: hip.attention_segments_shared(packed[:, :HD], pre[:, HD:2 * HD], pre[:, 2 * HD:], suf[:, HD:2 * HD], suf[:, 2 * HD:], slot, row0_t, sfx_off,
+                                                       sfx_len, H=H, D=D, T=T, P=P, n_slots=R, max_n=S, max_sfx=max_sfx, scale=D ** -0.5, out=out,
+                                                       kp_strides=(MLp * W, W), ks_strides=(MLs * W, W))
+        copies = lambda: hip.attention_segments(packed[:, :HD], cop[:, HD:2 * HD], cop[:, 2 * HD:], slot, row0_t, q_off, kv_len, H=H, D=D, T=T, n_slots=R, max_n=S,
+                                                max_kv=P + max_sfx, scale=D ** -0.5, out=out, k_strides=(MLc * W, W), v_strides=(MLc * W, W))
+        res = {}
+        try:
+            for rnd in range(3):
+                for name, opt, f in (("shared", -1, shared), ("copies", -1, copies), ("copies-split", 1, copies)):
+                    hip.set_option("attn_ksplit", opt)
+                    res.setdefault(name, []).append(timed_h(f))
+        finally:
+            hip.set_option("attn_ksplit", -1)
+        copies()
+        auto = hip.lib().stllm_last_kernel().decode()
+        fmt = lambda n: f"{min(res[n]):7.1f} us (" + " ".join(f"{x:.1f}" for x in res[n]) + ")"
+        print(f"segments on a shared base R={R} T={T} P={P} sfx_off={','.join(map(str, offs))} n={','.join(map(str, ns))}: shared {fmt('shared')}  "
+              f"attention_segments on copies: auto {fmt('copies')} -> {auto}, key split forced {fmt('copies-split')}"
+              f"  K/V bytes shared {(P + sum(o + n for o, n in zip(offs, ns))) * 2 * HD * 2 / 1e6:.1f} MB vs copies {sum(P + o + n for o, n in zip(offs, ns)) * 2 * HD * 2 / 1e6:.1f} MB",
+              flush=True)
+    sys.exit(0)
 if "--segments" in sys.argv:
     # --segments [P1,P2,...:n1,n2,...] (repeatable; default: 15 one-token segments behind 560 .. 1100 positions plus one 40-token segment behind 580): the packed
     # admission step of serving.Engine — segment r appends n_r rows behind P_r cached positions of its own slot.

@@ -34,6 +34,9 @@ ap.add_argument("--serve", default="", help="N,K: N questions behind one prefill
                                             "generate(batching='ragged') in waves of K; mixed answer lengths (printed), EOS disabled, useful tokens/s of both")
 ap.add_argument("--state", choices=["host", "device", "both"], default="host", help="with --serve: serving.Engine(state=...); 'both' alternates the host-state and the "
                 "device-state Engine in one process (one warm-up and three runs each, no waves) and times the hip.select_slots launch alone")
+ap.add_argument("--share-base", action="store_true", help="with --serve: serving.Engine(base=prefix) (the slots read ONE copy of the prefix, DESIGN.md §4.2j) against "
+                "the copying Engine (KVCache.load_row per admission), alternating in one process, one warm-up and three runs each, with --state host, device or both; "
+                "prints peak torch.cuda.max_memory_allocated of every run as well")
 ap.add_argument("--admit", default="", help="R,n: the whole admission step — R running rows behind 560 .. 1100 positions plus one admitted n-token row: "
                                             "LlamaModel.step_segments against extend(lengths=[0] * R + [n]) followed by a decode_step, alternating")
 ap.add_argument("--prefix-len", type=int, default=576, help="positions of the shared prefix of --share-prefix")
@@ -234,8 +237,9 @@ def serve_e2e(N, K):
     alens = [SERVE_LENGTHS[i % len(SERVE_LENGTHS)] for i in range(N)]
     qs = [torch.randn(n, 4096, device=dev) * 0.02 for n in qlens]
 
-    def engine(state=args.state):
-        eng = serving.Engine(model, K, P + max(qlens) + max(alens), eos_token_id=None, repetition_penalty=1.5, **({"state": state} if state != "host" else {}))
+    def engine(state=args.state, share=False):
+        eng = serving.Engine(model, K, P + max(qlens) + max(alens), eos_token_id=None, repetition_penalty=1.5, **({"state": state} if state != "host" else {}),
+                             **({"base": prefix} if share else {}))
         for q, n in zip(qs, alens):
             eng.submit(q, prefix=prefix, max_new_tokens=n)
         out = eng.run()
@@ -252,6 +256,8 @@ def serve_e2e(N, K):
                 mask[i, :q.shape[0]] = 1
             model.generate(inputs_embeds=emb, attention_mask=mask, batching="ragged", prefix_cache=prefix, max_new_tokens=n_new, eos_token_id=None,
                            repetition_penalty=1.5)
+    if args.share_base:
+        return serve_share_base(N, K, P, alens, engine)
     if args.state == "both":
         return serve_states(N, K, P, alens, engine)
     res, steps = {}, None
@@ -268,6 +274,28 @@ def serve_e2e(N, K):
         extra = f"{steps['segments']} admission + {steps['decode']} decode steps" if name == "engine" else f"{wave_steps} decode steps in {-(-N // K)} waves"
         print(f"{N} questions over {K} slots behind a {P}-token prefix, answers {','.join(map(str, alens))} ({sum(alens)} tokens), weights {args.weights} [{name}]: "
               f"{t * 1e3:.1f} ms = {sum(alens) / t:.1f} useful tok/s, {extra} (runs {' '.join(f'{x * 1e3:.1f}' for x in ts)})", flush=True)
+
+
+def serve_share_base(N, K, P, alens, engine):
+    """the copying Engine against Engine(base=prefix) on the same requests, per state: alternating, one warm-up and three runs each; wall time, useful tokens/s,
+    step counts and the peak of torch.cuda.max_memory_allocated over each run (the model, the prefix and the requests are allocated before and count in both)"""
+    states = ("host", "device") if args.state == "both" else (args.state,)
+    res, steps, peak = {}, {}, {}
+    for key in [(st, sh) for st in states for sh in (False, True)] * 4:
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+        steps[key] = engine(key[0], share=key[1])
+        torch.cuda.synchronize()
+        res.setdefault(key, []).append(time.perf_counter() - t0)
+        peak[key] = max(peak.get(key, 0), torch.cuda.max_memory_allocated())
+    print(f"allocated before any Engine (model, prefix, requests): {torch.cuda.memory_allocated() / 2 ** 20:.0f} MiB", flush=True)
+    for (st, sh), ts in res.items():
+        t = sorted(ts[1:])[1]
+        print(f"{N} questions over {K} slots behind a {P}-token prefix, answers {','.join(map(str, alens))} ({sum(alens)} tokens), weights {args.weights} "
+              f"[engine state={st} {'base=prefix' if sh else 'copies'}]: median {t * 1e3:.1f} ms = {sum(alens) / t:.1f} useful tok/s, "
+              f"{steps[(st, sh)]['segments']} admission + {steps[(st, sh)]['decode']} decode steps, peak allocated {peak[(st, sh)] / 2 ** 20:.0f} MiB "
+              f"(warm-up {ts[0] * 1e3:.1f}, runs {' '.join(f'{x * 1e3:.1f}' for x in ts[1:])})", flush=True)
 
 
 def serve_states(N, K, P, alens, engine):
