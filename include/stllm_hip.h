@@ -642,6 +642,26 @@ int stllm_kv_append_segments(int dtype, const void* src, int64_t ld_src, void* c
                              int max_n, int hidden, int max_len, void* stream);
 
 /*
+ * In-place re-order of the cache rows of beam groups (additive to ABI 7): what beam search's `past.index_select(0, beam_idx)` does to one
+ * layer buffer, for the rows and positions that can differ only.  The `rows` cache rows come in groups of nb consecutive rows, group g = rows
+ * [g*nb, (g+1)*nb).  src: int32 [rows], lo / hi: int32 [rows / nb], all in device memory.  For every group g, every row r of it with src[r] != r and every
+ * position p in [max(lo[g], 0), min(hi[g], capacity)) (positions of the buffer itself: local ones for a cache with a base) the [k | v] columns of
+ * cache[r*batch_stride + p*row_stride ..] receive what the same columns of cache[src[r]*batch_stride + p*row_stride ..] held BEFORE the call.  src may be
+ * any mapping inside a group (a fan-out, a cycle, a mix).  A src[r] outside its own group is taken as r, so a bad table cannot reach another group's rows.
+ * max_span: the host-known bound of the CLAMPED range's length, min(hi[g], capacity) - max(lo[g], 0) (hi[g] - lo[g] bounds it); it sizes the grid, which
+ * counts from the clamped start: positions at or behind max(lo[g], 0) + max_span are not moved.
+ * Schedule: one thread owns one 16-byte cell (position, column piece) of a group; it loads the cell from all nb rows, then stores the rows whose source
+ * differs.  No other thread touches that cell in any row of the group: no scratch buffer, no second launch, no barrier, no atomics — the same call on
+ * the same bytes gives the same bytes.  nb <= 16 (the cells live in registers); anything else returns STLLM_ERR_UNSUPPORTED and writes nothing.
+ * Dtypes (it moves bytes), strides and alignment as for stllm_kv_append_rows; rows % nb == 0, rows / nb <= 65535.
+ * Memory regions.  Never read: the q columns; positions outside [lo[g], hi[g]); every row of a group with hi[g] <= lo[g] or whose src is the identity.
+ * (A group that moves anything reads the range of ALL its nb rows, also rows that are nobody's source: bytes are moved, never interpreted.)  Never
+ * written: the q columns, positions outside the range, rows with src[r] == r, rows whose src[r] lies outside their own group, groups with hi[g] <= lo[g].
+ */
+int stllm_kv_reorder_rows(int dtype, void* cache, int64_t batch_stride, int64_t row_stride, const int32_t* src, const int32_t* lo, const int32_t* hi,
+                          int rows, int nb, int hidden, int capacity, int max_span, void* stream);
+
+/*
  * stllm_attention_segments on a SHARED BASE (additive to ABI 7; always causal): the R segments of a packed query buffer all sit behind the same
  * P prefix keys — ONE row of a base buffer (kp / vp, row strides kp_rs / vp_rs) that is only read — and each reads its own suffix keys in row slot[r] of the
  * slot buffers (ks / vs, (slot, row) strides).  The four int32 [R] device tables are those of stllm_attention_segments in SUFFIX-LOCAL positions:
@@ -811,6 +831,39 @@ typedef struct stllm_select_slots_args {
   float* aux;                /* nullable, [n_slots, 4] */
 } stllm_select_slots_args;
 int stllm_select_slots(const stllm_select_slots_args* args, void* stream);
+
+/*
+ * Beam-search candidates with per-row state (serving.Engine(num_beams > 1, state="device"); additive to ABI 7): stllm_beam_candidates for
+ * the beam rows of a continuous batch, each request at its own step.  ONE launch, one workgroup per candidate row; staging, reductions and error behaviour
+ * are stllm_beam_candidates' (the row body is the same kernel template).  (V + ld_prev) * 4 bytes must fit the LDS limit of stllm_select_tokens — a whole
+ * history, whatever the rows hold in this step: otherwise STLLM_ERR_UNSUPPORTED.
+ *
+ * src[r] is the row of `logits` that candidate row r reads in this step; src[r] < 0 or >= n_logits_rows: the row is NOT SERVED — nothing of it is read
+ * (not its n_prev, prev, beam_score) and nothing is written.  Several rows may name the same logits row (the admission step: all beams of a request start
+ * from the prompt's one row); rows are only read.  A served row r, c = n_prev[r] clamped to [0, ld_prev]:
+ *   cand_score[r, :k], cand_token[r, :k] = what stllm_beam_candidates gives for logits row src[r] with prev = prev[r, :c], n_prev = c,
+ *   suppress_eos = (eos_id >= 0 && n_prev[r] < min_length) and beam_score[r] — bit for bit a stllm_beam_candidates launch of that row alone.
+ * Never read: logits columns >= V and rows that no src names; prev[r, j] for j >= n_prev[r] (they may hold anything).  Never written: logits, src, prev,
+ * n_prev, beam_score; cand_score / cand_token of a row that is not served.
+ */
+typedef struct stllm_beam_rows_args {
+  const float* logits;       /* [n_logits_rows, ldl] fp32 */
+  int64_t ldl;               /* row stride in floats (>= V; any alignment) */
+  int n_logits_rows, V;
+  int rows;                  /* candidate rows */
+  const int32_t* src;        /* [rows] logits row of the candidate row in this step; outside [0, n_logits_rows): not served */
+  const int32_t* prev;       /* [rows, ld_prev] int32 ids generated so far; may be NULL when ld_prev == 0 */
+  int64_t ld_prev;
+  const int32_t* n_prev;     /* [rows] */
+  float penalty;             /* 1: none */
+  int min_length;
+  int eos_id;                /* < 0: none */
+  const float* beam_score;   /* [rows] */
+  int k;
+  float* cand_score;         /* [rows, k] */
+  int32_t* cand_token;       /* [rows, k] */
+} stllm_beam_rows_args;
+int stllm_beam_candidates_rows(const stllm_beam_rows_args* args, void* stream);
 
 /* =========================================================================================================================
  * Backward / optimizer entry points.  The reference has no such code of its own: the gradients come

@@ -158,12 +158,15 @@ class Chat:
                                   temperature=temperature, share_prefix=share_prefix)
 
     def answer_queue(self, img_list, questions_ids, slots=8, max_new_tokens=300, min_length=1, top_p=0.9, repetition_penalty=1.0, temperature=1.0,
-                     max_length=2000, do_sample=False, stop_sequences=None, instruction=False, prefix=None, generators=None, share_prefix=False, **kw):
+                     max_length=2000, do_sample=False, stop_sequences=None, instruction=False, prefix=None, generators=None, share_prefix=False,
+                     num_beams=1, length_penalty=1, **kw):
         """N >= 1 questions about ONE video through `slots` KV-cache slots (serving.Engine): a question whose answer ends frees its slot
         for the next one while the others keep decoding, so N may exceed `slots` and no row decodes padding.  answer_many's truncation rule, its
         repetition_penalty = 1.5 override and Chat's stop tokens as per-request stop_sequences.  prefix: a prefill_video(img_list) result — the video's K / V
         rows are copied into a slot on admission and only [BOS] + question runs.  generators: one torch.Generator per question for do_sample.  Returns one
-        (text, ids) per question, in order, each what answer() returns for that question alone.  num_beams == 1; **kw reaches the Engine's options.
+        (text, ids) per question, in order, each what answer() returns for that question alone.  **kw reaches the Engine's options (state="device").
+        num_beams > 1 (demo.py decodes with 5): every question searches num_beams beams in its slot, by answer()'s beam rules (do_sample
+        raises); length_penalty as in answer().
         share_prefix=True (needs prefix=): the prefix's cache becomes the Engine's base — no slot copies the video's rows, every step reads
         them once for all slots."""
         from . import serving
@@ -177,7 +180,8 @@ class Chat:
         P = cache.len if cache is not None else 0
         eng = serving.Engine(self.LLM, min(slots, len(embs)), P + max(e.shape[0] for e in embs) + max_new_tokens, device=embs[0].device,
                              max_new_tokens=max_new_tokens, do_sample=do_sample, min_length=min_length, top_p=top_p, repetition_penalty=repetition_penalty,
-                             temperature=temperature, stop_sequences=stop_sequences, **(dict(kw, base=cache) if share_prefix else kw))
+                             temperature=temperature, stop_sequences=stop_sequences, num_beams=num_beams, length_penalty=length_penalty,
+                             **(dict(kw, base=cache) if share_prefix else kw))
         handles = [eng.submit(e, prefix=cache, generator=None if generators is None else generators[i]) for i, e in enumerate(embs)]
         out = dict(eng.run())
         return [self._decoded(out[h]) for h in handles]

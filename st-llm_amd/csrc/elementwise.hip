@@ -1,6 +1,6 @@
 // HBM-bound glue kernels: row gather (token-block assembly / masking / embedding lookup),
 // temporal mean, ViT CLS rows, MVM cosine loss rows.  All fp32, float4-vectorised, coalesced.
-// Below them: token selection on a logits row held in the LDS (stllm_select_tokens, stllm_beam_candidates).
+// Below them: the KV-cache append / re-order copies, and token selection on a logits row held in the LDS (stllm_select_tokens, stllm_beam_candidates).
 #include "common.h"
 
 namespace {
@@ -154,6 +154,80 @@ __global__ __launch_bounds__(256) void kv_append_segments_kernel(const char* __r
   if (ps < 0 || ps >= max_len) return;
   const uint4 v = reinterpret_cast<const uint4*>(src + (int64_t)(r0 + i) * src_stride + col0_bytes)[c];
   reinterpret_cast<uint4*>(cache + (int64_t)sl * batch_stride + ps * row_stride + col0_bytes)[c] = v;
+}
+
+// in-place re-order of the cache rows of beam groups (stllm_kv_reorder_rows): group g = blockIdx.y is rows [g * nb, (g + 1) * nb), row r takes the [k | v]
+// bytes of row src[r] at the positions [max(lo[g], 0), min(hi[g], capacity)).  One thread owns one 16-byte cell (position, column piece) of the group:
+// it loads the cell from all nb rows, then stores the rows whose source differs — no other thread touches that cell in any row of the group, so a cycle
+// needs no scratch and no barrier.  cell[] and l[] are indexed with compile-time indices only (unrolled to kReorderMaxBeams, predicated on j < nb: the
+// table is uniform over the block, so the predicates are scalar branches) and stay in registers.  `cache` is deliberately not __restrict__: the stores
+// alias the loads, and every load stays in front of every store.  A src entry outside its own group is the identity.
+constexpr int kReorderMaxBeams = 16;
+
+// the per-row steps as compile-time recursions over the row index: every cell[] / l[] index is a constant in the source, whatever the unroller decides
+template <int J>
+__device__ __forceinline__ void reorder_table(int (&l)[kReorderMaxBeams], bool& any, const int32_t* src, int row0, int nb) {
+  if constexpr (J < kReorderMaxBeams) {
+    l[J] = J;
+    if (J < nb) {
+      const int s = src[row0 + J] - row0;   // local to the group; outside it: the identity
+      if (s >= 0 && s < nb) l[J] = s;
+      any = any || l[J] != J;
+    }
+    reorder_table<J + 1>(l, any, src, row0, nb);
+  }
+}
+
+template <int J>
+__device__ __forceinline__ void reorder_load(uint4 (&cell)[kReorderMaxBeams], const uint4* p, int64_t rs16, int nb) {
+  if constexpr (J < kReorderMaxBeams) {
+    if (J < nb) cell[J] = p[J * rs16];
+    reorder_load<J + 1>(cell, p, rs16, nb);
+  }
+}
+
+// cell[l] as a chain of selects on VALUES (l is uniform: scalar compares): branches that each store cell[I] are merged by the optimiser into one store
+// of cell[l] with a run-time index, which puts the array into scratch
+template <int I>
+__device__ __forceinline__ uint4 reorder_pick(const uint4 (&cell)[kReorderMaxBeams], int l, int nb, uint4 v) {
+  if constexpr (I < kReorderMaxBeams) {
+    if (I < nb) {
+      const bool hit = l == I;
+      v.x = hit ? cell[I].x : v.x; v.y = hit ? cell[I].y : v.y; v.z = hit ? cell[I].z : v.z; v.w = hit ? cell[I].w : v.w;
+    }
+    return reorder_pick<I + 1>(cell, l, nb, v);
+  } else {
+    return v;
+  }
+}
+
+template <int J>
+__device__ __forceinline__ void reorder_store(const uint4 (&cell)[kReorderMaxBeams], const int (&l)[kReorderMaxBeams], uint4* p, int64_t rs16, int nb) {
+  if constexpr (J < kReorderMaxBeams) {
+    if (J < nb && l[J] != J) p[J * rs16] = reorder_pick<0>(cell, l[J], nb, cell[J]);
+    reorder_store<J + 1>(cell, l, p, rs16, nb);
+  }
+}
+
+__global__ __launch_bounds__(256) void kv_reorder_rows_kernel(char* cache, int64_t batch_stride, int64_t row_stride, const int32_t* __restrict__ src,
+                                                              const int32_t* __restrict__ lo, const int32_t* __restrict__ hi, int nb, int capacity,
+                                                              int col0_bytes, int n16) {
+  const int g = blockIdx.y;
+  const int p0 = max(lo[g], 0), p1 = min(hi[g], capacity);
+  if (p1 <= p0) return;
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t ps = p0 + c / n16;
+  if (ps >= p1) return;
+  const int col = (int)(c % n16);
+  int l[kReorderMaxBeams];                        // source of row j, local to the group; j: nothing to do
+  bool any = false;
+  reorder_table<0>(l, any, src, g * nb, nb);
+  if (!any) return;
+  uint4* cellp = reinterpret_cast<uint4*>(cache + (int64_t)g * nb * batch_stride + ps * row_stride + col0_bytes) + col;
+  const int64_t rs16 = batch_stride / 16;         // between the rows of the group, in cells
+  uint4 cell[kReorderMaxBeams];
+  reorder_load<0>(cell, cellp, rs16, nb);
+  reorder_store<0>(cell, l, cellp, rs16, nb);
 }
 
 // ---- token selection: stllm_select_tokens / stllm_beam_candidates (include/stllm_hip.h) --------------------------------------------------------------
@@ -389,12 +463,33 @@ __global__ __launch_bounds__(kSelThreads) void select_kernel(const typename SelA
   }
 }
 
-__global__ __launch_bounds__(kSelThreads) void beam_candidates_kernel(const stllm_beam_args a) {
+// One kernel body for stllm_beam_candidates (ROWS = false: workgroup = row r of every table, one n_prev and one EOS suppression for the launch) and
+// stllm_beam_candidates_rows (ROWS = true: workgroup = candidate row, which reads logits row src[row] behind its own history length and EOS suppression).
+// What differs is set once at the top; everything behind it is the same code.
+template <bool ROWS> struct BeamArgs { typedef stllm_beam_args type; };
+template <> struct BeamArgs<true> { typedef stllm_beam_rows_args type; };
+
+template <bool ROWS>
+__global__ __launch_bounds__(kSelThreads) void beam_kernel(const typename BeamArgs<ROWS>::type a) {
   extern __shared__ float smem[];                 // [V] scores, then [n_prev] penalised values
   __shared__ SelRed red;
   const int row = blockIdx.x, tid = threadIdx.x, V = a.V;
   float* s = smem;
-  const float* x = a.logits + (int64_t)row * a.ldl;
+  const float* x;
+  int n_prev;
+  bool suppress_eos;
+  if constexpr (ROWS) {
+    const int r = a.src[row];
+    if (r < 0 || r >= a.n_logits_rows) return;    // not served in this step (uniform over the block): nothing else is read
+    const int n = a.n_prev[row];
+    x = a.logits + (int64_t)r * a.ldl;
+    n_prev = min(max(n, 0), (int)a.ld_prev);
+    suppress_eos = a.eos_id >= 0 && n < a.min_length;
+  } else {
+    x = a.logits + (int64_t)row * a.ldl;
+    n_prev = a.n_prev;
+    suppress_eos = a.suppress_eos;
+  }
   int ph = 0;
   float bv = -INFINITY, bi = kSelNoIndex;
   for (int c = tid; c < V; c += kSelThreads) {
@@ -409,8 +504,8 @@ __global__ __launch_bounds__(kSelThreads) void beam_candidates_kernel(const stll
   const float lse = logf(sel_block_sum(z, &red, ph));
   for (int c = tid; c < V; c += kSelThreads) s[c] = (s[c] - mx) - lse;   // log_softmax
   __syncthreads();
-  if (a.penalty != 1.0f && a.n_prev > 0) sel_penalise(s, s + V, a.prev + (int64_t)row * a.ld_prev, a.n_prev, V, a.penalty);
-  if (a.suppress_eos && tid == 0 && (unsigned)a.eos_id < (unsigned)V) s[a.eos_id] = -INFINITY;
+  if (a.penalty != 1.0f && n_prev > 0) sel_penalise(s, s + V, a.prev + (int64_t)row * a.ld_prev, n_prev, V, a.penalty);
+  if (suppress_eos && tid == 0 && (unsigned)a.eos_id < (unsigned)V) s[a.eos_id] = -INFINITY;
   __syncthreads();
   const float bs = a.beam_score[row];
   for (int c = tid; c < V; c += kSelThreads) s[c] += bs;
@@ -485,15 +580,74 @@ extern "C" int stllm_beam_candidates(const stllm_beam_args* a, void* stream) {
   bool lds_first;
   const int lds_d = lds_dev.enter(&lds_first);
   if (lds_first || lds > lds_dev.value[lds_d]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(beam_candidates_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(beam_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
       stllm_set_error("stllm_beam_candidates: cannot opt into %d bytes of LDS", lds);
       return STLLM_ERR_UNSUPPORTED;
     }
     lds_dev.value[lds_d] = lds;
     lds_dev.done(lds_d);
   }
-  hipLaunchKernelGGL(beam_candidates_kernel, dim3(a->rows), dim3(kSelThreads), lds, reinterpret_cast<hipStream_t>(stream), *a);
+  hipLaunchKernelGGL(beam_kernel<false>, dim3(a->rows), dim3(kSelThreads), lds, reinterpret_cast<hipStream_t>(stream), *a);
   STLLM_CHECK_LAUNCH("stllm_beam_candidates");
+  return STLLM_OK;
+}
+
+extern "C" int stllm_beam_candidates_rows(const stllm_beam_rows_args* a, void* stream) {
+  STLLM_CHECK_ARG(a != nullptr, "stllm_beam_candidates_rows: null args");
+  STLLM_CHECK_ARG(a->logits && a->beam_score && a->cand_score && a->cand_token && a->n_logits_rows > 0 && a->V > 0 && a->ldl >= a->V,
+                  "stllm_beam_candidates_rows: bad pointers / n_logits_rows=%d V=%d ldl=%lld", a->n_logits_rows, a->V, (long long)a->ldl);
+  STLLM_CHECK_ARG(a->rows > 0 && a->src && a->n_prev, "stllm_beam_candidates_rows: bad src / n_prev / rows=%d", a->rows);
+  STLLM_CHECK_ARG(a->k >= 1 && a->k <= 32 && a->k <= a->V, "stllm_beam_candidates_rows: 1 <= k=%d <= min(32, V=%d)", a->k, a->V);
+  STLLM_CHECK_ARG(a->ld_prev >= 0 && (a->ld_prev == 0 || a->prev), "stllm_beam_candidates_rows: prev needs ld_prev >= 0 (NULL only with ld_prev == 0)");
+  STLLM_CHECK_ARG(a->penalty > 0.0f, "stllm_beam_candidates_rows: penalty must be positive");
+  const int64_t need = ((int64_t)a->V + a->ld_prev) * 4;   // the row and a whole history, whatever the rows hold in this step
+  if (need > kSelLdsBytes) {
+    stllm_set_error("stllm_beam_candidates_rows: V=%d + ld_prev=%lld floats do not fit %d bytes of LDS", a->V, (long long)a->ld_prev, kSelLdsBytes);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  const int lds = (int)((need + 15) & ~(int64_t)15);
+  static StllmPerDevice lds_dev;   // largest dynamic-LDS size opted into, per device ordinal
+  bool lds_first;
+  const int lds_d = lds_dev.enter(&lds_first);
+  if (lds_first || lds > lds_dev.value[lds_d]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(beam_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+      stllm_set_error("stllm_beam_candidates_rows: cannot opt into %d bytes of LDS", lds);
+      return STLLM_ERR_UNSUPPORTED;
+    }
+    lds_dev.value[lds_d] = lds;
+    lds_dev.done(lds_d);
+  }
+  hipLaunchKernelGGL(beam_kernel<true>, dim3(a->rows), dim3(kSelThreads), lds, reinterpret_cast<hipStream_t>(stream), *a);
+  STLLM_CHECK_LAUNCH("stllm_beam_candidates_rows");
+  return STLLM_OK;
+}
+
+extern "C" int stllm_kv_reorder_rows(int dtype, void* cache, int64_t batch_stride, int64_t row_stride, const int32_t* src, const int32_t* lo,
+                                     const int32_t* hi, int rows, int nb, int hidden, int capacity, int max_span, void* stream) {
+  STLLM_CHECK_ARG(cache && src && lo && hi, "stllm_kv_reorder_rows: null pointer");
+  STLLM_CHECK_ARG(rows > 0 && nb >= 1 && rows % nb == 0 && rows / nb <= 65535 && hidden > 0 && capacity > 0 && max_span > 0,
+                  "stllm_kv_reorder_rows: bad rows=%d nb=%d hidden=%d capacity=%d max_span=%d (rows a multiple of nb, rows / nb <= 65535)", rows, nb, hidden,
+                  capacity, max_span);
+  if (nb > kReorderMaxBeams) {
+    stllm_set_error("stllm_kv_reorder_rows: nb=%d rows per group, at most %d are held in registers", nb, kReorderMaxBeams);
+    return STLLM_ERR_UNSUPPORTED;
+  }
+  int e;
+  switch (dtype) {
+    case STLLM_BF16: case STLLM_F16: e = 2; break;
+    case STLLM_F32: e = 4; break;
+    default: stllm_set_error("stllm_kv_reorder_rows: bad dtype %d", dtype); return STLLM_ERR_BAD_DTYPE;
+  }
+  STLLM_CHECK_ARG(row_stride >= 3 * (int64_t)hidden && batch_stride >= (int64_t)capacity * row_stride,
+                  "stllm_kv_reorder_rows: rows of 3 * hidden elements, capacity rows per cache row");
+  STLLM_CHECK_ARG(((int64_t)hidden * e) % 16 == 0 && (row_stride * e) % 16 == 0 && (batch_stride * e) % 16 == 0 && aligned16(cache) &&
+                      ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(lo) | reinterpret_cast<uintptr_t>(hi)) & 3) == 0,
+                  "stllm_kv_reorder_rows: 16-byte vector copies need 16-byte aligned pointers, strides and hidden");
+  const int col0 = hidden * e, n16 = (2 * hidden * e) / 16;
+  const int64_t cells = (int64_t)(max_span < capacity ? max_span : capacity) * n16;
+  hipLaunchKernelGGL(kv_reorder_rows_kernel, dim3((unsigned)((cells + 255) / 256), rows / nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     reinterpret_cast<char*>(cache), batch_stride * e, row_stride * e, src, lo, hi, nb, capacity, col0, n16);
+  STLLM_CHECK_LAUNCH("stllm_kv_reorder_rows");
   return STLLM_OK;
 }
 

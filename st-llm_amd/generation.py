@@ -400,6 +400,84 @@ def _device_candidates(logits, ids, beam_scores, B, nb, *, repetition_penalty, s
     return cs, ct, cb
 
 
+class _BeamRequest:
+    """_generate_beams for ONE prompt, a step at a time: the state (ids, beam scores, hypotheses) and the scorer (BeamSearchScorer.process / finalize) of row b
+    of its batch, for a caller whose prompts are each at their own step (serving.Engine(num_beams > 1)).  Every line is the one _generate_beams runs for
+    B = 1 — _BeamHypotheses with the request's length_penalty, EOS candidates beyond rank num_beams skipped, is_done, the stop sequences, the open beams
+    becoming hypotheses at max_new_tokens, EOS appended when the best hypothesis ended early — so a request gives the ids of generate() for it alone.
+    device: where ids and beam scores live (the logits' device for the torch chain; the CPU when the candidates come from the device kernel, whose
+    caller reads nothing else back)."""
+
+    def __init__(self, opts, max_new_tokens, device):
+        nb = self.nb = opts.num_beams
+        self.o, self.max_new = opts, max_new_tokens
+        self.ids = torch.zeros((nb, 0), dtype=torch.long, device=device)
+        self.beam_scores = torch.zeros(nb, dtype=torch.float32, device=device)
+        self.beam_scores[1:] = -1e9
+        self.hyps = _BeamHypotheses(nb, opts.length_penalty)
+        self.done = self.finished = False
+
+    def candidates(self, logits):
+        """the torch chain of _generate_beams' non-device branch on this request's [num_beams, V] logits rows: CPU (scores, tokens, beams) [2 * num_beams]"""
+        o, nb, cur_len = self.o, self.nb, self.ids.shape[1]
+        logp = logits.to(self.ids.device).log_softmax(dim=-1)
+        logp = _process_logits(logp, self.ids, cur_len, o.repetition_penalty, o.min_length, o.eos_token_id)
+        V = logp.shape[-1]
+        cand = (logp + self.beam_scores[:, None]).view(1, nb * V)
+        cand_scores, cand_tokens = torch.topk(cand, 2 * nb, dim=1, largest=True, sorted=True)
+        cand_beams = torch.div(cand_tokens, V, rounding_mode="floor")
+        return cand_scores[0].cpu(), (cand_tokens % V)[0].cpu(), cand_beams[0].cpu()
+
+    @staticmethod
+    def merge(scores, tokens, nb, V):
+        """_device_candidates' merge for one prompt: scores f32 / tokens [nb * k] (beam-major, k = 2 * nb per beam) on the CPU -> the first k of their union
+        under (score descending, beam * V + token ascending): (scores, tokens, beams) [k]"""
+        k = 2 * nb
+        beam = torch.arange(nb).repeat_interleave(k)
+        order = sorted(range(nb * k), key=lambda i: (-float(scores[i]), int(beam[i]) * V + int(tokens[i])))[:k]
+        return scores[order], tokens[order].long(), beam[order]
+
+    def process(self, cs, ct, cb):
+        """BeamSearchScorer.process on the 2 * num_beams merged candidates (CPU tensors), then the stop rules.  Returns (next tokens, beam indices): lists
+        of num_beams ints, beam j continues beam index[j] with token[j]; sets `finished`."""
+        o, nb, cur_len, dev = self.o, self.nb, self.ids.shape[1], self.ids.device
+        eos = o.eos_token_id
+        scores, tokens, index = [], [], []
+        for rank in range(2 * nb):
+            tok, sc, row = int(ct[rank]), float(cs[rank]), int(cb[rank])
+            if eos is not None and tok == eos:
+                if rank >= nb:
+                    continue
+                self.hyps.add(self.ids[row].clone(), sc)
+            else:
+                scores.append(sc); tokens.append(tok); index.append(row)
+            if len(tokens) == nb:
+                break
+        self.done = self.hyps.is_done(float(cs.max()), cur_len)
+        self.beam_scores = torch.tensor(scores, dtype=torch.float32, device=dev)
+        self.ids = torch.cat([self.ids[torch.tensor(index, device=dev)], torch.tensor(tokens, device=dev).view(-1, 1)], dim=-1)
+        if o.stop_sequences and not self.done and bool(_ends_in_stop(self.ids[:1], o.stop_sequences)[0]):
+            for j in range(nb):
+                self.hyps.add(self.ids[j].clone(), scores[j])
+            self.done = True
+        self.finished = self.done or _stop(o.stopping_criteria, self.ids, None) or self.ids.shape[1] >= self.max_new
+        return tokens, index
+
+    def finalize(self):
+        """BeamSearchScorer.finalize: the 1-D LongTensor generate(...)[0] returns for this prompt alone"""
+        o = self.o
+        if not self.done:
+            for j in range(self.nb):
+                self.hyps.add(self.ids[j], float(self.beam_scores[j]))
+        best = sorted(self.hyps.beams, key=lambda x: x[0])[-1][1]
+        sent_max = min(len(best) + 1, self.max_new)
+        res = torch.full((sent_max,), o.pad_token_id, dtype=torch.long, device=self.ids.device)
+        res[:len(best)] = best
+        if len(best) < sent_max:
+            res[len(best)] = o.eos_token_id
+        return res
+
+
 def _generate_device(lm_wrapper, inputs_embeds, opts, prefix, lengths):
     """greedy search / sampling of generate(selection="device"): one hip.select_tokens launch per step, the ids stay on the device"""
     from . import hip

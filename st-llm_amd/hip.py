@@ -32,7 +32,7 @@ EXPORTS = ["stllm_last_error", "stllm_abi_version", "stllm_last_kernel", "stllm_
            "stllm_attention_shared_workspace_bytes", "stllm_attention_shared", "stllm_select_tokens", "stllm_beam_candidates",
            "stllm_attention_offset_ragged_workspace_bytes", "stllm_attention_offset_ragged", "stllm_kv_append_spans",
            "stllm_attention_segments_workspace_bytes", "stllm_attention_segments", "stllm_kv_append_segments", "stllm_select_slots",
-           "stllm_attention_segments_shared_workspace_bytes", "stllm_attention_segments_shared"]
+           "stllm_attention_segments_shared_workspace_bytes", "stllm_attention_segments_shared", "stllm_kv_reorder_rows", "stllm_beam_candidates_rows"]
 
 
 def torch_dtype(d):
@@ -95,6 +95,13 @@ class BeamArgs(ctypes.Structure):
     _fields_ = [("logits", c_void_p), ("ldl", c_int64), ("rows", c_int), ("V", c_int), ("prev", c_void_p), ("ld_prev", c_int64), ("n_prev", c_int),
                 ("penalty", c_float), ("suppress_eos", c_int), ("eos_id", c_int), ("beam_score", c_void_p), ("k", c_int), ("cand_score", c_void_p),
                 ("cand_token", c_void_p)]
+
+
+class BeamRowsArgs(ctypes.Structure):
+    """stllm_beam_rows_args (include/stllm_hip.h)"""
+    _fields_ = [("logits", c_void_p), ("ldl", c_int64), ("n_logits_rows", c_int), ("V", c_int), ("rows", c_int), ("src", c_void_p), ("prev", c_void_p),
+                ("ld_prev", c_int64), ("n_prev", c_void_p), ("penalty", c_float), ("min_length", c_int), ("eos_id", c_int), ("beam_score", c_void_p),
+                ("k", c_int), ("cand_score", c_void_p), ("cand_token", c_void_p)]
 
 
 class VitBlockWeights(ctypes.Structure):
@@ -231,6 +238,8 @@ def _bind(L, strict=True):
     B("stllm_select_tokens", [ctypes.POINTER(SelectArgs), c_void_p])
     B("stllm_beam_candidates", [ctypes.POINTER(BeamArgs), c_void_p])
     B("stllm_select_slots", [ctypes.POINTER(SelectSlotsArgs), c_void_p])
+    B("stllm_beam_candidates_rows", [ctypes.POINTER(BeamRowsArgs), c_void_p])
+    B("stllm_kv_reorder_rows", [c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p])
     B("stllm_gemm_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     B("stllm_gemm_w4_plan", [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
     return L
@@ -1236,6 +1245,28 @@ def kv_append_segments(src, cache, slot, row0, pos0, n, *, T, max_n):
     return cache
 
 
+def beam_rows_available(device):
+    """kv_reorder_rows and beam_candidates_rows can serve tensors on `device`: a device check, nothing more (as segments_available).
+    serving.Engine(num_beams > 1) asks before it allocates anything; a stand-in for this module that states the two contracts answers for itself."""
+    return torch.device(device).type == "cuda"
+
+
+def kv_reorder_rows(cache, src, lo, hi, *, nb, max_span):
+    """stllm_kv_reorder_rows: the rows of cache [rows, capacity, 3*hidden] (one layer buffer) come in groups of nb; row r takes the [k | v] bytes of row
+    src[r] (int32 [rows] on the device, any mapping inside a group; outside it: identity) at the positions [lo[g], hi[g]) of its group (int32 [rows / nb],
+    clamped to [0, capacity); hi - lo <= max_span), in place, in ONE launch without scratch.  nb <= 16.  All compute dtypes."""
+    _req(src, torch.int32, "src"); _req(lo, torch.int32, "lo"); _req(hi, torch.int32, "hi")
+    if cache.dim() != 3 or cache.stride(2) != 1 or cache.shape[2] % 3:
+        raise RuntimeError(f"kv_reorder_rows: cache must be [rows, capacity, 3*hidden] with unit column stride, got {tuple(cache.shape)}")
+    rows, capacity, D3 = cache.shape
+    if nb < 1 or rows % nb or src.numel() != rows or lo.numel() != rows // nb or hi.numel() != rows // nb or not (src.is_contiguous() and lo.is_contiguous() and
+                                                                                                         hi.is_contiguous()):
+        raise RuntimeError(f"kv_reorder_rows: {rows} rows in groups of {nb}: src {tuple(src.shape)}, lo {tuple(lo.shape)}, hi {tuple(hi.shape)}")
+    _check(lib().stllm_kv_reorder_rows(dtype_code(cache.dtype), _p(cache), cache.stride(0), cache.stride(1), _p(src), _p(lo), _p(hi), rows, int(nb), D3 // 3,
+                                       capacity, int(max_span), _stream()), "stllm_kv_reorder_rows")
+    return cache
+
+
 def gather_rows(src_a, idx_a, *, src_b=None, add=None, idx_add=None, out=None, scale=1.0):
     """out[i] = scale * ((idx_a[i] >= 0 ? src_a[idx_a[i]] : src_b[-idx_a[i]-1]) (+ add[idx_add[i]]))."""
     _req(src_a, torch.float32, "src_a"); _req(idx_a, torch.int32, "idx_a")
@@ -1351,6 +1382,50 @@ def beam_candidates(logits, beam_score, k, *, prev=None, n_prev=0, penalty=1.0, 
                  n_prev=n_prev, penalty=penalty, suppress_eos=int(bool(suppress_eos)), eos_id=-1 if eos_id is None else int(eos_id),
                  beam_score=beam_score.data_ptr(), k=int(k), cand_score=cand_score.data_ptr(), cand_token=cand_token.data_ptr())
     _check(lib().stllm_beam_candidates(ctypes.byref(a), _stream()), "stllm_beam_candidates")
+    return cand_score, cand_token
+
+
+SEL_LDS_BYTES = 160 * 1024 - 4096   # kSelLdsBytes of csrc/elementwise.hip: the dynamic LDS that a row of a selection launch may take
+
+
+def beam_rows_fit(V, ld_prev):
+    """whether stllm_beam_candidates_rows takes rows of V logits behind a history table of ld_prev columns: V + ld_prev floats in the LDS, whatever the
+    rows hold.  serving.Engine(num_beams > 1, state="device") asks when a request is submitted, so that no launch in the middle of a run raises."""
+    return (int(V) + int(ld_prev)) * 4 <= SEL_LDS_BYTES
+
+
+def beam_candidates_rows(logits, src, beam_score, k, *, prev=None, n_prev, penalty=1.0, min_length=0, eos_id=None, cand_score=None, cand_token=None):
+    """stllm_beam_candidates_rows: beam_candidates for the beam rows of a continuous batch.  logits f32 [n_logits_rows, V]; src int32 [rows]: candidate row
+    r reads logits row src[r] (outside [0, n_logits_rows): not served, its outputs untouched; several rows may name one logits row); prev int32
+    [rows, ld_prev] and n_prev int32 [rows]: row r's history is prev[r, :n_prev[r]]; EOS is suppressed while n_prev[r] < min_length; beam_score f32 [rows].
+    -> (cand_score f32 [rows, k], cand_token int32 [rows, k]), a served row bit-equal to beam_candidates of that row alone.  V + ld_prev floats that do not
+    fit the LDS raise."""
+    _req(logits, torch.float32, "logits")
+    if logits.dim() != 2:
+        raise RuntimeError(f"beam_candidates_rows: logits must be [n_logits_rows, V], got {tuple(logits.shape)}")
+    n_rows, V = logits.shape
+    ldl = logits.stride(0) if n_rows > 1 else max(logits.stride(0), V)
+    _req(src, torch.int32, "src"); _req(n_prev, torch.int32, "n_prev"); _req(beam_score, torch.float32, "beam_score")
+    rows = src.numel()
+    if src.dim() != 1 or n_prev.numel() != rows or beam_score.numel() != rows or not (src.is_contiguous() and n_prev.is_contiguous() and beam_score.is_contiguous()):
+        raise RuntimeError(f"beam_candidates_rows: src, n_prev and beam_score must be contiguous [{rows}]")
+    ld_prev = 0
+    if prev is not None:
+        _req(prev, torch.int32, "prev")
+        if prev.dim() != 2 or prev.shape[0] != rows or not prev.is_contiguous():
+            raise RuntimeError(f"beam_candidates_rows: prev must be contiguous int32 [{rows}, ld_prev], got {tuple(prev.shape)}")
+        ld_prev = prev.shape[1]
+    if cand_score is None:
+        cand_score = torch.empty((rows, k), dtype=torch.float32, device=logits.device)
+    if cand_token is None:
+        cand_token = torch.empty((rows, k), dtype=torch.int32, device=logits.device)
+    _req(cand_score, torch.float32, "cand_score"); _req(cand_token, torch.int32, "cand_token")
+    if tuple(cand_score.shape) != (rows, k) or tuple(cand_token.shape) != (rows, k) or not cand_score.is_contiguous() or not cand_token.is_contiguous():
+        raise RuntimeError(f"beam_candidates_rows: cand_score / cand_token must be contiguous [{rows}, {k}]")
+    a = BeamRowsArgs(logits=logits.data_ptr(), ldl=ldl, n_logits_rows=n_rows, V=V, rows=rows, src=src.data_ptr(), prev=prev.data_ptr() if ld_prev else None,
+                     ld_prev=ld_prev, n_prev=n_prev.data_ptr(), penalty=penalty, min_length=int(min_length), eos_id=-1 if eos_id is None else int(eos_id),
+                     beam_score=beam_score.data_ptr(), k=int(k), cand_score=cand_score.data_ptr(), cand_token=cand_token.data_ptr())
+    _check(lib().stllm_beam_candidates_rows(ctypes.byref(a), _stream()), "stllm_beam_candidates_rows")
     return cand_score, cand_token
 
 

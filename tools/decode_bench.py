@@ -22,7 +22,8 @@ ap.add_argument("--questions", default="", help="L1,L2,...: N questions of these
 ap.add_argument("--share-prefix", action="store_true", help="with --questions or --beams: generate(share_prefix=True) against share_prefix=False (private copies), "
                                                           "alternating; tokens/s and peak memory_allocated of both")
 ap.add_argument("--beams", type=int, default=0, help="with --share-prefix: one prompt of --prefix-len + 24 positions, this many beams (5 = demo.py); "
-                                                    "with --generate: num_beams of one prompt")
+                                                    "with --generate: num_beams of one prompt; with --serve N,K: every question searches this many beams "
+                                                    "(serving.Engine(num_beams=...), DESIGN.md §4.2k; see --serve)")
 ap.add_argument("--generate", type=int, default=0, help="N: end-to-end generate() of N new tokens per row behind a 576-position prompt (--rows prompts, or one prompt x --beams), "
                                                        "tokens/s, and the selection step alone in us by device events, on the logits of that prompt")
 ap.add_argument("--selection", choices=["torch", "device", "both"], default="both", help="with --generate: the selection mode; 'both' alternates them, 3 repeats each")
@@ -31,7 +32,11 @@ ap.add_argument("--cases", default="", help="with --generate: several workloads 
                                             "rows, b = beams of one prompt; default: the one case --rows / --sample / --beams describe")
 ap.add_argument("--sync-every", type=int, default=1, help="with --generate, selection 'device': generate(sync_every=K)")
 ap.add_argument("--serve", default="", help="N,K: N questions behind one prefilled --prefix-len prefix through K slots of serving.Engine (continuous batching) against "
-                                            "generate(batching='ragged') in waves of K; mixed answer lengths (printed), EOS disabled, useful tokens/s of both")
+                                            "generate(batching='ragged') in waves of K; mixed answer lengths (printed), EOS disabled, useful tokens/s of both.  "
+                                            "With --beams nb > 1 the run is the beam comparison instead: the Engine(num_beams=nb) in both states (and, with "
+                                            "--share-base, with base=prefix as well) against generate(num_beams=nb) one question at a time and in waves of K, "
+                                            "alternating, one warm-up and three runs each, and the kv_reorder_rows launch alone against the index_select "
+                                            "assignment; --state is ignored there")
 ap.add_argument("--state", choices=["host", "device", "both"], default="host", help="with --serve: serving.Engine(state=...); 'both' alternates the host-state and the "
                 "device-state Engine in one process (one warm-up and three runs each, no waves) and times the hip.select_slots launch alone")
 ap.add_argument("--share-base", action="store_true", help="with --serve: serving.Engine(base=prefix) (the slots read ONE copy of the prefix, DESIGN.md §4.2j) against "
@@ -276,6 +281,90 @@ def serve_e2e(N, K):
               f"{t * 1e3:.1f} ms = {sum(alens) / t:.1f} useful tok/s, {extra} (runs {' '.join(f'{x * 1e3:.1f}' for x in ts)})", flush=True)
 
 
+def serve_beams(N, K, nb):
+    """--serve N,K --beams nb: §4.2h's workload with nb beams per question.  Alternating in one process, one warm-up and three runs each:
+    (a) serving.Engine(num_beams=nb) in both states (with --share-base also Engine(base=prefix)), (b) generate(num_beams=nb) one question at a time,
+    (c) generate(num_beams=nb, batching="ragged") in waves of K questions.  Then the re-order kernel alone against the index_select assignment of
+    _CacheStepper.advance: nb rows, --llm-layers layer buffers, spans of 16 and 256 positions, device events around blocks of 20 re-orders."""
+    from stllm_amd import serving
+    P = args.prefix_len
+    video = torch.randn(1, P, 4096, device=dev) * 0.02
+    prefix = lm.new_cache(1, P, dev)
+    lm.prefill(video, None, cache=prefix)
+    qlens = [9 + (5 * i) % 17 for i in range(N)]
+    alens = [SERVE_LENGTHS[i % len(SERVE_LENGTHS)] for i in range(N)]
+    qs = [torch.randn(n, 4096, device=dev) * 0.02 for n in qlens]
+    kw = dict(eos_token_id=None, repetition_penalty=1.5, num_beams=nb)
+    steps = {}
+
+    def engine(state, share):
+        eng = serving.Engine(model, K, P + max(qlens) + max(alens), state=state, **({"base": prefix} if share else {}), **kw)
+        for q, n in zip(qs, alens):
+            eng.submit(q, prefix=prefix, max_new_tokens=n)
+        out = eng.run()
+        assert sorted(ids.numel() for _, ids in out) == sorted(alens)
+        steps[(state, share)] = dict(eng.steps)
+
+    def one_at_a_time():
+        for q, n in zip(qs, alens):
+            model.generate(inputs_embeds=q[None], prefix_cache=prefix, max_new_tokens=n, **kw)
+
+    def waves():
+        for w in range(0, N, K):
+            rows, n_new = qs[w:w + K], max(alens[w:w + K])
+            emb = torch.zeros(len(rows), max(q.shape[0] for q in rows), 4096, device=dev)
+            mask = torch.zeros(emb.shape[:2], dtype=torch.long)
+            for i, q in enumerate(rows):
+                emb[i, :q.shape[0]] = q
+                mask[i, :q.shape[0]] = 1
+            model.generate(inputs_embeds=emb, attention_mask=mask, batching="ragged", prefix_cache=prefix, max_new_tokens=n_new, **kw)
+    runs = [(f"engine state={st} {'base=prefix' if sh else 'copies'}", (lambda st=st, sh=sh: engine(st, sh)))
+            for st in ("host", "device") for sh in ((False, True) if args.share_base else (False,))]
+    runs += [(f"generate(num_beams={nb}) one question at a time", one_at_a_time), (f"generate(num_beams={nb}) in waves of {K}", waves)]
+    res = {}
+    for name, f in runs * 4:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        res.setdefault(name, []).append(time.perf_counter() - t0)
+    for name, ts in res.items():
+        t = sorted(ts[1:])[1]
+        print(f"{N} questions x {nb} beams over {K} slots ({K * nb} rows) behind a {P}-token prefix, answers {','.join(map(str, alens))} ({sum(alens)} tokens), "
+              f"weights {args.weights} [{name}]: median {t * 1e3:.1f} ms = {sum(alens) / t:.1f} useful tok/s (warm-up {ts[0] * 1e3:.1f}, runs "
+              f"{' '.join(f'{x * 1e3:.1f}' for x in ts[1:])})", flush=True)
+    print("engine steps:", {f"{st} {'base' if sh else 'copies'}": s for (st, sh), s in steps.items()}, flush=True)
+    # the re-order alone: one request's nb rows, a cycle (every row moves), all layer buffers
+    L = args.llm_layers
+    for span in (16, 256):
+        cap = 64 + span
+        bufs = [torch.randn(nb, cap, 3 * 4096, device=dev).to(torch.bfloat16) for _ in range(L)]
+        perm = [(i + 1) % nb for i in range(nb)]
+        src, idx = torch.tensor(perm, dtype=torch.int32, device=dev), torch.tensor(perm, device=dev)
+        lo, hi = torch.tensor([64], dtype=torch.int32, device=dev), torch.tensor([cap], dtype=torch.int32, device=dev)
+
+        def kernel():
+            for b in bufs:
+                hip.kv_reorder_rows(b, src, lo, hi, nb=nb, max_span=span)
+
+        def index_select():
+            for b in bufs:
+                b[:, :cap] = b[:, :cap].index_select(0, idx)
+        us = {}
+        for name, f in (("kv_reorder_rows", kernel), ("index_select assignment", index_select)) * 3:
+            f()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(20):
+                f()
+            e1.record()
+            e1.synchronize()
+            us.setdefault(name, []).append(e0.elapsed_time(e1) / 20 * 1e3)
+        for name, v in us.items():
+            print(f"re-order alone, {nb} rows, {L} layers, bf16, span {span} of {cap} positions [{name}]: {sorted(v)[1]:.1f} us per re-order of all layers "
+                  f"(blocks {' '.join(f'{x:.1f}' for x in v)})", flush=True)
+
+
 def serve_share_base(N, K, P, alens, engine):
     """the copying Engine against Engine(base=prefix) on the same requests, per state: alternating, one warm-up and three runs each; wall time, useful tokens/s,
     step counts and the peak of torch.cuda.max_memory_allocated over each run (the model, the prefix and the requests are allocated before and count in both)"""
@@ -377,6 +466,9 @@ def admit_step(R, n):
           f" — the parent pair also decodes the admitted row's first token", flush=True)
 
 
+if args.serve and args.beams:
+    serve_beams(*[int(x) for x in args.serve.split(",")], args.beams)
+    sys.exit(0)
 if args.serve:
     serve_e2e(*[int(x) for x in args.serve.split(",")])
     sys.exit(0)
